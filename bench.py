@@ -8,7 +8,8 @@ sampling + log-prob), GAE + value targets, then E=10 epochs x 8 minibatches of 6
 flat gradient per optimizer step).  Inputs are resident in HBM before timing starts.
 value = N_gpus * 4096 * 128 * steps / max-over-ranks wall time (weak scaling: envs per GPU fixed).
 
-Also reported on the same JSON line:
+A plain run sets up, warms up, times the steps, writes the last timed iteration's outputs when
+--dump-outputs DIR is given, and prints the JSON line.  With --full the same line also carries:
   roofline      the dominant kernel instantiation (most device time in the timed region), from
                 HIP events on its dispatch packets (hipExtLaunchKernelGGL) recorded live:
                 algorithmic FLOPs or bytes per launch / mean launch time vs the MI355X peak;
@@ -39,6 +40,7 @@ METRICS = {"mlp": METRIC,
 PEAK_FP32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: F32 MFMA = vector peak (dense)
 PEAK_BF16_MFMA_TFLOPS = 2516.6  # MI355X_MICROARCH.md: bf16 dense (2.5 PF; sparsity excluded)
 PEAK_HBM_GBS = 8000.0           # MI355X HBM3E spec
+DUMP_MAX_ELEMS = 1 << 20        # --dump-outputs: larger entries are sampled (12 entries < 64 MB)
 
 
 def parse():
@@ -67,6 +69,19 @@ def parse():
                    help="fc-layer GEMM precision: bf16 (default; bf16 operands, f32 accumulate, f32 "
                         "master params -- BASELINE.json configs[1]) or f32 (bit-level parity "
                         "mode with the reference's f32 CPU trainer)")
+    p.add_argument("--full", action="store_true",
+                   default=os.environ.get("PPO_BENCH_FULL") == "1",
+                   help="(or PPO_BENCH_FULL=1, for scripts that run many lines) also measure "
+                        "everything beside the headline figure: per-kernel event timing "
+                        "(roofline, gae_roofline, scan sweep), the f32 / host-pool / "
+                        "BASELINE-config legs and the CPU baseline (each still has its own "
+                        "--no-... switch).  Without it the run sets up, warms up, times --steps "
+                        "iterations and prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed iteration returned (the "
+                        "rollout buffer's entries, the minibatch losses) and the parameters it "
+                        "left as DIR/<name>.npy (float32 / float64; an entry above "
+                        f"{DUMP_MAX_ELEMS} elements as a fixed seeded sample of it)")
     p.add_argument("--cpu-baseline", dest="cpu_baseline", action="store_true", default=True)
     p.add_argument("--no-cpu-baseline", dest="cpu_baseline", action="store_false")
     p.add_argument("--cpu-rollout-steps", type=int, default=128)
@@ -94,6 +109,8 @@ def parse():
                         "humanoid, cnn, lstm; empty for none)")
     args = p.parse_args()
     apply_model_defaults(args, p.get_default)
+    if not args.full:
+        args.no_timing, args.no_legs, args.cpu_baseline = True, True, False
     return args
 
 
@@ -326,7 +343,14 @@ def build(args, precision, env_kind, dev, rank):
                    feature_extractor={"lstm": "LSTM", "cnn": "CNN"}.get(args.model, "MLP"),
                    latent=args.latent)
     torch.manual_seed(0)  # identical initial parameters on every rank
-    agent = make_agent(run, device=dev)
+    # ... and in every run: the orthogonal init's host QR returns other last bits with another
+    # number of BLAS threads, so the parameters are drawn on one thread whatever the host offers
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        agent = make_agent(run, device=dev)
+    finally:
+        torch.set_num_threads(threads)
     if args.model == "cnn":
         from mujoco_reinforcement_learning_amd.cnn import SyntheticPixelVecEnvHelper
         streams = make_synthetic_streams(n, t, 1, seed=1000 + rank, device=dev)
@@ -342,9 +366,10 @@ def build(args, precision, env_kind, dev, rank):
     return run, agent, helper, algo
 
 
-def time_iterations(algo, steps, warmup, world, dev) -> float:
+def time_iterations(algo, steps, warmup, world, dev):
     """W untimed iterations, then K timed ones bracketed by barrier + synchronize; the max over
-    ranks of the wall time."""
+    ranks of the wall time, and what the last timed iteration returned (memory, loss_buf)."""
+    last = None
     for _ in range(warmup):
         algo._iterate()
     torch.cuda.synchronize()
@@ -352,7 +377,7 @@ def time_iterations(algo, steps, warmup, world, dev) -> float:
         torch.distributed.barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        algo._iterate()
+        last = algo._iterate()
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
@@ -361,7 +386,32 @@ def time_iterations(algo, steps, warmup, world, dev) -> float:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(tt)
-    return elapsed
+    return elapsed, last
+
+
+def dump_outputs(path, memory, loss_buf, agent) -> None:
+    """--dump-outputs: every entry of the buffer the last timed iteration returned (the reference's
+    keys and env-major shapes), its per-minibatch losses and the parameters it left, one
+    DIR/<name>.npy each; float64 stays, everything else is written as float32.  An entry above
+    DUMP_MAX_ELEMS elements is written as a sample of it at fixed seeded positions (sorted flat
+    indices of the entry's shape, drawn with replacement)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    entries = {k: memory[k] for k in memory.keys()}
+    entries["minibatch_losses"] = loss_buf
+    entries["params"] = agent.flat_params
+    for name, x in entries.items():
+        x = x.detach()
+        if x.numel() > DUMP_MAX_ELEMS:
+            flat = np.sort(np.random.RandomState(0).randint(0, x.numel(), DUMP_MAX_ELEMS))
+            flat = torch.from_numpy(flat).to(x.device)
+            idx = []
+            for d in reversed(x.shape):
+                idx.append(flat % d)
+                flat = flat // d
+            x = x[tuple(reversed(idx))]
+        x = x.to(torch.float64 if x.dtype == torch.float64 else torch.float32)
+        np.save(os.path.join(path, f"{name}.npy"), x.cpu().numpy())
 
 
 def leg(args, precision, env_kind, dev) -> dict:
@@ -369,7 +419,7 @@ def leg(args, precision, env_kind, dev) -> dict:
     _progress(f"leg: precision {precision}, env {env_kind}")
     run, agent, helper, algo = build(args, precision, env_kind, dev, 0)
     try:
-        elapsed = time_iterations(algo, args.leg_steps, 2, 1, dev)  # eager, then graph capture
+        elapsed, _ = time_iterations(algo, args.leg_steps, 2, 1, dev)  # eager, then graph capture
     finally:
         if hasattr(helper, "close"):
             helper.close()
@@ -577,7 +627,7 @@ def config_leg(args, name, dev, steps=None, **over) -> dict:
               f"hidden {ns.hidden}, B {ns.batch}, model {ns.model}")
     run, agent, helper, algo = build(ns, ns.precision, "device", dev, 0)
     try:
-        elapsed = time_iterations(algo, steps, 2, 1, dev)  # warm-up 2: eager, then graph capture
+        elapsed, _ = time_iterations(algo, steps, 2, 1, dev)  # warm-up 2: eager, then graph capture
         kernels = {}
         if hasattr(agent.engine, "timing"):
             ec = run.engine_config
@@ -712,9 +762,12 @@ def main():
     hidden = tuple(int(h) for h in args.hidden.split(","))
     n, t = args.num_envs, args.horizon
     run, agent, helper, algo = build(args, args.precision, args.env, dev, rank)
-    elapsed = time_iterations(algo, args.steps, args.warmup, world, dev)
+    elapsed, last = time_iterations(algo, args.steps, args.warmup, world, dev)
     if rank == 0:
         _progress(f"timed: {1000 * elapsed / args.steps:.2f} ms per iteration")
+        if args.dump_outputs and last is not None:
+            dump_outputs(args.dump_outputs, *last, agent)
+    del last
     comm = None
     if hasattr(algo, "dp"):
         # the exchange as it ran: the native communicator's own rank count (ppo_comm_query), the

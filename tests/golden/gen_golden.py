@@ -28,6 +28,8 @@ import torch
 
 REF_SRC = "/root/reference/src"
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "reference_mlp.npz")
+# cases written to a file of their own (each fixture file stays below 1 MiB)
+OUT_SPLIT = {"ant_relu_2x256": OUT.replace(".npz", "_ant.npz")}
 FULL_PARAMS_LIMIT = 200_000
 
 CASES = [
@@ -98,8 +100,10 @@ def main():
                 out[f"{name}/{k}"] = arr
         out[f"{name}/meta"] = np.array([seed, obs, window, act, len(hidden), len(critic_hidden),
                                         *hidden, *critic_hidden], dtype=np.int64)
-    np.savez_compressed(OUT, **out)
-    print("wrote", OUT, sum(v.nbytes for v in out.values()), "bytes raw")
+    for path in (OUT, *OUT_SPLIT.values()):
+        part = {k: v for k, v in out.items() if OUT_SPLIT.get(k.split("/")[0], OUT) == path}
+        np.savez_compressed(path, **part)
+        print("wrote", path, sum(v.nbytes for v in part.values()), "bytes raw")
 
 
 if __name__ == "__main__":

@@ -16,11 +16,28 @@ failure to the first step that diverges.
 """
 from __future__ import annotations
 
+import os
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from oracle import ppo_ref as R
+
+# the reference modules' recorded init and forward (tests/golden/gen_golden.py), one file per
+# group of cases so that each stays a small fixture
+GOLDEN_MLP = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", f)
+              for f in ("reference_mlp.npz", "reference_mlp_ant.npz")]
+
+
+def load_golden_mlp() -> dict:
+    """{"<case>/<entry>": array} over every file of the MLP fixture."""
+    out = {}
+    for path in GOLDEN_MLP:
+        with np.load(path) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
+
 
 EPS_FLIP = 1e-3          # |g| < EPS_FLIP * max|g| of the tensor at some step -> sign-flip-prone
 MAX_OUTSIDE_FRACTION = 1e-3  # flip-prone elements actually outside rtol: at most 0.1 % of all

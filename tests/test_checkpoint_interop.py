@@ -3,121 +3,142 @@
 
 tests/golden/engine_ckpt/ was written on the GPU box by PPOEngineAgent.save() after one PPO
 iteration on the engine (tools/make_engine_ckpt.py; actor 2x64, critic the reference's [128, 128],
-W=1).  Here, where /root/reference exists (skipped elsewhere), the files are loaded with
-weights_only=True into models.linear.actor.Actor / models.critic.Critic and torch.optim.Adam,
-and must reproduce the engine's recorded forward (rtol 1e-5: HIP vs CPU summation order) and its
-next Adam step (<= 2 ulp); the engine's configurations.json must restore through the reference's
-positional Run.get_configurations.
+W=1).  The reference's side is recorded in tests/golden/reference_interop.npz
+(tests/golden/gen_interop_golden.py, run where the reference sources are): the state_dict keys and
+shapes of its models.linear.actor.Actor / models.critic.Critic (what a strict load_state_dict
+accepts), their forward on the probe input after loading the checkpoint with weights_only=True,
+the parameters after the next step of torch.optim.Adam restored from the checkpoint, and what its
+positional Run.get_configurations restores.  Here the checkpoint must carry exactly those keys
+and shapes; the recorded reference forward must reproduce the engine's recorded forward (rtol
+1e-5: HIP vs CPU summation order); torch.optim.Adam, restored from the checkpoint here, must
+reproduce the engine's next Adam step (<= 2 ulp) and the recorded reference-side step (bitwise);
+and configurations.json must hold every section's values in the reference's field order.
 """
+import json
 import os
-import sys
 
 import numpy as np
-import pytest
 import torch
 
-REF_SRC = "/root/reference/src"
-FIXTURE = os.path.join(os.path.dirname(__file__), "golden", "engine_ckpt")
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_SRC) or not os.path.isdir(FIXTURE),
-                                reason="needs the reference sources and the engine fixture")
+HERE = os.path.dirname(os.path.abspath(__file__))
+FIXTURE = os.path.join(HERE, "golden", "engine_ckpt")
+GOLD = np.load(os.path.join(HERE, "golden", "reference_interop.npz"))
 
 
-@pytest.fixture()
-def reference():
-    sys.path.insert(0, REF_SRC)
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    from entities import features as F
-    from gen_golden import _make_run
-    from models.critic import Critic
-    from models.linear.actor import Actor
-    yield F, _make_run, Actor, Critic
-    F.Run._instances.clear()
+def _recorded_layout(prefix):
+    """[(state_dict key, shape)] of the reference's modules, in their order."""
+    shapes = json.loads(str(GOLD[f"{prefix}/shapes"]))
+    return [(str(k), tuple(s)) for k, s in zip(GOLD[f"{prefix}/keys"], shapes)]
 
 
-def test_reference_modules_load_engine_checkpoint(reference):
-    F, make_ref_run, Actor, Critic = reference
+def test_reference_modules_load_engine_checkpoint():
+    from oracle import ppo_ref as R
     probe = np.load(os.path.join(FIXTURE, "probe.npz"))
     path = os.path.join(FIXTURE, "networks", str(int(probe["episode"])))
-    make_ref_run(17, 1, 6, [64, 64], "ReLU")
-    nets = torch.nn.ModuleDict()
-    nets["actor"] = Actor()
-    nets["critic"] = Critic()
-    nets.load_state_dict(torch.load(f"{path}/networks.pth", weights_only=True))  # strict keys
-    x = torch.from_numpy(probe["x"])
-    with torch.no_grad():
-        mean, std = nets["actor"](x)
-        value = nets["critic"](x)[:, 0, :]
+    sd = torch.load(f"{path}/networks.pth", weights_only=True)
+    # strict keys: exactly the reference modules' entries, in their shapes
+    assert [(k, tuple(v.shape)) for k, v in sd.items()] == _recorded_layout("mlp")
+    # the reference modules' forward on the loaded parameters (recorded) against the engine's
+    mean, std, value = (torch.from_numpy(GOLD[f"mlp/{k}"]) for k in ("mean", "std", "value"))
     torch.testing.assert_close(mean, torch.from_numpy(probe["mean"]), rtol=1e-5, atol=1e-6)
     torch.testing.assert_close(value, torch.from_numpy(probe["value"]), rtol=1e-5, atol=1e-6)
     assert torch.equal(std, torch.from_numpy(probe["std"]))
-    opts = {k: torch.optim.Adam(nets[k].parameters(), lr=1.0) for k in ("actor", "critic")}
+    # ... and the oracle's restated modules take the same file strictly and compute the same
+    oracle = R.RefAgent(R.RefConfig(obs_dim=17, act_dim=6, window=1, actor_hidden=(64, 64),
+                                    critic_hidden=(128, 128)))
+    oracle.networks.load_state_dict(sd)
+    x = torch.from_numpy(probe["x"])
+    with torch.no_grad():
+        m2, s2 = oracle.networks["actor"](x)
+        v2 = oracle.networks["critic"](x).reshape(len(x), 1)
+    torch.testing.assert_close(m2, mean, rtol=1e-6, atol=1e-7)
+    torch.testing.assert_close(v2, value, rtol=1e-6, atol=1e-7)
+    assert torch.equal(s2, std)
+    # the optimizer files restore torch.optim.Adam over the modules' parameters (their order)
+    params = [(str(k), torch.nn.Parameter(sd[str(k)].clone())) for k in GOLD["mlp/param_keys"]]
+    opts = {name: torch.optim.Adam([p for k, p in params if k.startswith(name + ".")], lr=1.0)
+            for name in ("actor", "critic")}
     for k, o in opts.items():
         o.load_state_dict(torch.load(f"{path}/optimizer_{k}.pth", weights_only=True))
     assert opts["actor"].param_groups[0]["lr"] < 1.0  # the engine's (decayed) lr was restored
+    assert [opts[k].param_groups[0]["lr"] for k in ("actor", "critic")] == list(GOLD["mlp/lr"])
     grad = torch.from_numpy(probe["grad"])
     off = 0
-    for p in nets.parameters():
+    for _, p in params:
         p.grad = grad[off:off + p.numel()].view(p.shape).clone()
         off += p.numel()
+    assert off == grad.numel()
     opts["critic"].step()
     opts["actor"].step()
-    got = torch.cat([p.detach().flatten() for p in nets.parameters()])
+    got = torch.cat([p.detach().flatten() for _, p in params])
+    assert torch.equal(got, torch.from_numpy(GOLD["mlp/params_after"]))  # the reference-side step
     exp = torch.from_numpy(probe["params_after"])
     ulp = torch.finfo(torch.float32).eps * exp.abs().clamp_min(1e-30)
     assert bool(((got - exp).abs() <= 2 * ulp).all()), float(((got - exp).abs() / ulp).max())
 
 
-def test_reference_restores_engine_configurations(reference):
-    F, *_ = reference
-    F.Run._instances.clear()
-    run = F.Run.get_configurations(FIXTURE)  # positional restore (features.py:145-165)
-    assert run.network_config.input_shape == 17
-    assert run.network_config.linear_hidden_shapes == [64, 64]
-    assert run.network_config.activation_class is torch.nn.ReLU
-    assert run.dtype is torch.float32
+def test_reference_restores_engine_configurations():
+    """features.py:145-165 restores every section positionally (Section(*json_section.values()))
+    and Run from what remains: the file must hold the reference's fields, all of them, in its
+    order, and nothing else; the values it restores (recorded) are the engine run's."""
+    with open(os.path.join(FIXTURE, "configurations.json")) as fh:
+        cfg = json.load(fh)
+    assert list(cfg) == ["run"]
+    run = cfg["run"]
+    assert list(run) == [str(k) for k in GOLD["cfg/fields/run"]]
+    for section in ("rewards_config", "training_config", "ppo_config", "sac_config",
+                    "environment_config", "agent_config", "network_config", "dynamic_config"):
+        assert list(run[section]) == [str(k) for k in GOLD[f"cfg/fields/{section}"]], section
+    restored = json.loads(str(GOLD["cfg/restored"]))
+    assert restored["input_shape"] == 17 == run["network_config"]["input_shape"]
+    assert restored["linear_hidden_shapes"] == [64, 64]
+    assert restored["linear_hidden_shapes"] == run["network_config"]["linear_hidden_shapes"]
+    assert restored["activation_class"] == "ReLU" == run["network_config"]["activation_class"]
+    assert restored["dtype"] == "float32" == run["dtype"]
+    # the engine's own restore of the same file agrees with the reference's
+    from mujoco_reinforcement_learning_amd.features import Run
+    Run.reset_instance()
+    try:
+        mine = Run.get_configurations(FIXTURE)
+        assert mine.network_config.input_shape == restored["input_shape"]
+        assert mine.network_config.output_shape == restored["output_shape"]
+        assert list(mine.network_config.linear_hidden_shapes) == restored["linear_hidden_shapes"]
+        assert mine.network_config.activation_class is torch.nn.ReLU
+        assert mine.dtype is torch.float32
+        assert mine.environment_config.num_envs == restored["num_envs"]
+        assert mine.environment_config.window_length == restored["window_length"]
+    finally:
+        Run.reset_instance()
 
 
 def test_reference_lstm_modules_load_engine_state_dict(tmp_path):
     """The LSTM agent's networks (lstm.EngineLSTMActor / EngineLSTMCritic, the state_dict that
-    LSTMEngineAgent.save writes to networks.pth) load strictly into the reference's own
-    LSTMActor / LSTMCritic (weights_only), and the reference forward on those parameters equals
-    the oracle's restated BiLSTM forward."""
-    sys.path.insert(0, REF_SRC)
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    from entities import features as F
-    from gen_golden_lstm import _make_run
-    from models.lstm.lstm_actor import LSTMActor
-    from models.lstm.lstm_critic import LSTMCritic
+    LSTMEngineAgent.save writes to networks.pth) carry exactly the keys and shapes of the
+    reference's own LSTMActor / LSTMCritic (a strict, weights_only load), and the reference forward
+    on those parameters (recorded) equals the oracle's restated BiLSTM forward."""
     from mujoco_reinforcement_learning_amd.lstm import EngineLSTMActor, EngineLSTMCritic
     from oracle import lstm_ref as L
     from oracle.ppo_ref import RefConfig
-    try:
-        obs, window, act, latent, hidden = 17, 3, 6, 8, [16, 16]
-        torch.manual_seed(5)
-        nets = torch.nn.ModuleDict()
-        nets["actor"] = EngineLSTMActor(obs, latent, 1, window, hidden, act, torch.nn.ReLU, True,
-                                        0.01)
-        nets["critic"] = EngineLSTMCritic(obs, latent, hidden, torch.nn.ReLU, True, 0.01)
-        torch.save({k: v.detach().cpu() for k, v in nets.state_dict().items()},
-                   tmp_path / "networks.pth")
-        _make_run(obs, window, act, latent, 1, hidden, "ReLU")
-        ref = torch.nn.ModuleDict()
-        ref["actor"] = LSTMActor()
-        ref["critic"] = LSTMCritic()
-        ref.load_state_dict(torch.load(tmp_path / "networks.pth", weights_only=True))  # strict
-        cfg = RefConfig(obs_dim=obs, act_dim=act, window=window, actor_hidden=tuple(hidden),
-                        critic_hidden=tuple(hidden))
-        oracle = L.RefLSTMAgent(cfg, latent, 1)
-        oracle.networks.load_state_dict(torch.load(tmp_path / "networks.pth", weights_only=True))
-        x = torch.randn(9, window, obs, generator=torch.Generator().manual_seed(3))
-        with torch.no_grad():
-            mean, std_rep = ref["actor"](x)
-            value = ref["critic"](x)
-            m2, s2 = oracle.networks["actor"](x)
-            v2 = oracle.networks["critic"](x)
-        torch.testing.assert_close(mean, m2, rtol=1e-6, atol=1e-7)
-        torch.testing.assert_close(std_rep[0], s2, rtol=1e-6, atol=1e-7)
-        torch.testing.assert_close(value, v2, rtol=1e-6, atol=1e-7)
-    finally:
-        F.Run._instances.clear()
+    obs, window, act, latent, hidden = 17, 3, 6, 8, [16, 16]
+    torch.manual_seed(5)
+    nets = torch.nn.ModuleDict()
+    nets["actor"] = EngineLSTMActor(obs, latent, 1, window, hidden, act, torch.nn.ReLU, True,
+                                    0.01)
+    nets["critic"] = EngineLSTMCritic(obs, latent, hidden, torch.nn.ReLU, True, 0.01)
+    torch.save({k: v.detach().cpu() for k, v in nets.state_dict().items()},
+               tmp_path / "networks.pth")
+    saved = torch.load(tmp_path / "networks.pth", weights_only=True)
+    assert [(k, tuple(v.shape)) for k, v in saved.items()] == _recorded_layout("lstm")  # strict
+    # the parameters the reference modules were given when the fixture was recorded
+    params = {k: torch.from_numpy(GOLD[f"lstm/param/{k}"]) for k in saved}
+    cfg = RefConfig(obs_dim=obs, act_dim=act, window=window, actor_hidden=tuple(hidden),
+                    critic_hidden=tuple(hidden))
+    oracle = L.RefLSTMAgent(cfg, latent, 1)
+    oracle.networks.load_state_dict(params)
+    x = torch.from_numpy(GOLD["lstm/x"])
+    with torch.no_grad():
+        m2, s2 = oracle.networks["actor"](x)
+        v2 = oracle.networks["critic"](x)
+    torch.testing.assert_close(torch.from_numpy(GOLD["lstm/mean"]), m2, rtol=1e-6, atol=1e-7)
+    torch.testing.assert_close(torch.from_numpy(GOLD["lstm/std"]), s2, rtol=1e-6, atol=1e-7)
+    torch.testing.assert_close(torch.from_numpy(GOLD["lstm/value"]), v2, rtol=1e-6, atol=1e-7)

@@ -14,19 +14,16 @@ reference's own main.py network.
   modules (tests/golden/gen_golden.py), including the 3x512 Humanoid and main.py nets.
 """
 import hashlib
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import ppo_ref as R
-from parity_util import (compare_step_grads, make_pair, own_gae, record_oracle_steps,
-                         replay_rows, run_iteration_pair, stepwise_parity)
+from parity_util import (compare_step_grads, load_golden_mlp, make_pair, own_gae,
+                         record_oracle_steps, replay_rows, run_iteration_pair, stepwise_parity)
 
 pytestmark = pytest.mark.gpu
-
-GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "reference_mlp.npz")
 
 HUMANOID = dict(obs=376, act=17, hidden=(512, 512, 512))
 MAIN_PY = dict(obs=348, act=17, window=5, hidden=(256, 256, 128, 128), critic_hidden=(128, 128))
@@ -292,8 +289,7 @@ def test_full_size_iteration_properties(gpu, label, shape, n, precision):
 
 # --------------------------------------------- HIP forward against the reference's own outputs
 def _golden_cases():
-    z = np.load(GOLDEN)
-    return sorted({k.split("/")[0] for k in z.files})
+    return sorted({k.split("/")[0] for k in load_golden_mlp()})
 
 
 @pytest.mark.parametrize("name", _golden_cases())
@@ -308,7 +304,7 @@ def test_hip_forward_matches_reference_golden(gpu, name):
     last bits may differ on the GPU box's CPU -- far below the 1e-5 forward bar."""
     from mujoco_reinforcement_learning_amd.agent import PPOEngineAgent
     from mujoco_reinforcement_learning_amd.runconfig import make_run
-    z = np.load(GOLDEN)
+    z = load_golden_mlp()
     seed, obs, window, act, n_a, n_c, *widths = (int(v) for v in z[f"{name}/meta"])
     hidden, critic_hidden = widths[:n_a], widths[n_a:n_a + n_c]
     activation = str(z[f"{name}/activation"])
@@ -318,7 +314,7 @@ def test_hip_forward_matches_reference_golden(gpu, name):
     torch.manual_seed(seed)
     agent = PPOEngineAgent(run, device=gpu)
     sd = agent.networks.state_dict()
-    if all(f"{name}/{k}" in z.files for k in sd):
+    if all(f"{name}/{k}" in z for k in sd):
         agent.networks.load_state_dict({k: torch.from_numpy(z[f"{name}/{k}"]) for k in sd})
         for k, v in agent.networks.state_dict().items():
             digest = hashlib.sha256(v.detach().cpu().contiguous().numpy().tobytes()).hexdigest()

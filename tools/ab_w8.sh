@@ -3,6 +3,7 @@
 # LSTM line, the f32 leg and the CNN line.
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
+export PPO_BENCH_FULL=1  # = bench.py --full: the per-kernel figures and legs read below are measured only then
 mkdir -p gpurun_out
 for w in 0 1; do
   PPO_GEMM_W8=$w timeout -k 10 300 python bench.py --model lstm --steps 2 --warmup 1 > gpurun_out/ab_w8_${w}_lstm.json 2> gpurun_out/ab_w8_${w}_lstm.err || { tail -5 gpurun_out/ab_w8_${w}_lstm.err; exit 1; }

@@ -1,5 +1,6 @@
 # A/B of the Humanoid shard's layer-0 WGRAD split count (PPO_WIDE_SPLITS0 8 / 16)
 set -o pipefail
+export PPO_BENCH_FULL=1  # = bench.py --full: the per-kernel figures and legs read below are measured only then
 A="--num-envs 1024 --obs-dim 376 --act-dim 17 --hidden 512,512,512 --batch 8192 --steps 3 --warmup 1 --no-cpu-baseline --no-legs"
 for rep in 1 2; do
 for c in 8 16; do

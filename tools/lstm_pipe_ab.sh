@@ -1,5 +1,6 @@
 # A/B of the BiLSTM forward-step k-loop pipeline (PPO_LSTM_STEP_PIPE 1 / 2), alternating
 set -o pipefail
+export PPO_BENCH_FULL=1  # = bench.py --full: the per-kernel figures and legs read below are measured only then
 for rep in 1 2; do
 for c in 1 2; do
   PPO_LSTM_STEP_PIPE=$c timeout -k 10 300 python bench.py --model lstm --steps 3 --warmup 1 --no-cpu-baseline \

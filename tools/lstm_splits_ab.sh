@@ -1,5 +1,6 @@
 # A/B of the BiLSTM weight-gradient split count (PPO_LSTM_SPLITS), alternating, one process each
 set -o pipefail
+export PPO_BENCH_FULL=1  # = bench.py --full: the per-kernel figures and legs read below are measured only then
 for rep in 1 2; do
 for c in 32 16; do
   PPO_LSTM_SPLITS=$c timeout -k 10 300 python bench.py --model lstm --steps 3 --warmup 1 --no-cpu-baseline \
