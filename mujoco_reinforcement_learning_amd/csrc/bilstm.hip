@@ -42,6 +42,7 @@
 #include "common.h"
 #include "gemm.h"
 #include "gemm_ops.h"
+#include "ppo_loss.h"
 #include "reduce_slabs.h"
 #include "timing.h"
 #include "wide_gemm.h"
@@ -50,7 +51,6 @@
 namespace ppo {
 namespace lstm {
 
-constexpr int kMaxA = 32;
 constexpr int kSplits = 32;           // split-K slabs of the weight gradients (at most)
 constexpr int64_t kAlign = 16;        // floats: every flat tensor starts 64-B aligned
 constexpr int64_t kWsAlign = 64;
@@ -779,7 +779,7 @@ struct HeadArgs {
   const int32_t *rows;
   float *dzm, *dzs, *dv;  // [B][A], [B][A], [B]
   float *row_part;        // [B][3]: min(s1, s2), sum_a entropy, huber
-  float clip_lo, clip_hi, ent_coef, inv_b, inv_ba;
+  LossCoef coef;
   int b, a;
 };
 
@@ -797,10 +797,9 @@ __global__ __launch_bounds__(256) void lstm_policy_head_kernel(HeadArgs q) {
     if (q.std_out) q.std_out[idx] = sd;
     if (!q.action) continue;
     const float e = q.eps ? q.eps[idx] : philox_normal_at(q.seed, q.offset + idx);
-    const float x = e * sd + mu;
+    const float x = normal_sample(e, sd, mu);
     q.action[idx] = x;
-    const float d = x - mu;
-    lp += (((-(d * d)) / (2.f * (sd * sd))) - logf(sd)) - kLogSqrt2Pi;
+    lp += normal_logp_term(x - mu, sd * sd, logf(sd));
   }
   if (q.logp_out) q.logp_out[n] = lp;
   if (q.value_out) q.value_out[n] = q.value[n];
@@ -814,7 +813,7 @@ __global__ __launch_bounds__(256) void lstm_update_head_kernel(HeadArgs q) {
   const int A = q.a;
   const int64_t src = q.rows[n];
   float lp = 0.f, ent = 0.f;
-  float mu[kMaxA], sd[kMaxA], dd[kMaxA], uv[kMaxA];
+  float mu[kMaxAct], sd[kMaxAct], dd[kMaxAct], uv[kMaxAct];
   for (int k = 0; k < A; ++k) {
     const int64_t idx = static_cast<int64_t>(n) * A + k;
     mu[k] = q.mean[idx];
@@ -822,28 +821,17 @@ __global__ __launch_bounds__(256) void lstm_update_head_kernel(HeadArgs q) {
     sd[k] = 0.2f * expf(uv[k]);
     dd[k] = q.actions[src * A + k] - mu[k];
     const float ls = logf(sd[k]);
-    lp += (((-(dd[k] * dd[k])) / (2.f * (sd[k] * sd[k]))) - ls) - kLogSqrt2Pi;
+    lp += normal_logp_term(dd[k], sd[k] * sd[k], ls);
     ent += kEntropyConst + ls;
   }
-  const float adv = q.adv[src];
-  const float ratio = expf(lp - q.old_logp[src]);
-  const float s1 = ratio * adv;
-  const float cl = ratio < q.clip_lo ? q.clip_lo : (ratio > q.clip_hi ? q.clip_hi : ratio);
-  const float s2 = cl * adv;
-  const float mn = (s1 != s1 || s2 != s2) ? (s1 + s2) : (s2 < s1 ? s2 : s1);
-  const float gg = -q.inv_b;
-  const float g1 = (s1 < s2) ? gg : (s1 == s2 ? gg * 0.5f : 0.f);
-  const float g2 = (s2 < s1) ? gg : (s1 == s2 ? gg * 0.5f : 0.f);
-  const bool inside = (ratio >= q.clip_lo) && (ratio <= q.clip_hi);
-  const float dratio = g1 * adv + (inside ? g2 * adv : 0.f);
-  const float dlogp = dratio * ratio;
+  const Surrogate sg = clipped_surrogate(lp, q.old_logp[src], q.adv[src], q.coef);
   for (int k = 0; k < A; ++k) {
     const int64_t idx = static_cast<int64_t>(n) * A + k;
     const float var = sd[k] * sd[k];
-    const float dmu = dlogp * (dd[k] / var);
+    const float dmu = sg.dlogp * (dd[k] / var);
     // d/dstd of -(d^2)/(2 var) - log(std): d^2/std^3 - 1/std; entropy mean: -ent_coef/(B*A*std)
-    const float dstd = dlogp * ((dd[k] * dd[k]) / (var * sd[k]) - 1.f / sd[k]) -
-                       q.ent_coef * q.inv_ba / sd[k];
+    const float dstd = sg.dlogp * ((dd[k] * dd[k]) / (var * sd[k]) - 1.f / sd[k]) -
+                       q.coef.ent_coef * q.coef.inv_ba / sd[k];
     const float du = dstd * sd[k];  // std = 0.2 * exp(u)
     const float uu = uv[k];
     q.dzm[idx] = dmu * (1.f - mu[k] * mu[k]);
@@ -851,11 +839,10 @@ __global__ __launch_bounds__(256) void lstm_update_head_kernel(HeadArgs q) {
   }
   const float v = q.value[n];
   const float diff = v - q.vt[src];
-  const float ad = fabsf(diff);
-  q.dv[n] = q.inv_b * (diff < -1.f ? -1.f : (diff > 1.f ? 1.f : diff));
-  q.row_part[3 * n] = mn;
+  q.dv[n] = huber_grad(diff, q.coef.inv_b);
+  q.row_part[3 * n] = sg.mn;
   q.row_part[3 * n + 1] = ent;
-  q.row_part[3 * n + 2] = (ad < 1.f) ? 0.5f * ad * ad : (ad - 0.5f);
+  q.row_part[3 * n + 2] = huber(diff);
 }
 
 // loss scalars: one block, fixed-order strided sums + tree (deterministic)
@@ -1553,7 +1540,7 @@ int forward_all(ppo_lstm_ctx *x, const float *xin, const __bf16 *xin16, int b, h
 extern "C" int ppo_lstm_ctx_create(const ppo_lstm_cfg *cfg, int device, ppo_lstm_ctx **out) {
   PPO_REQUIRE(cfg != nullptr && out != nullptr, "ppo_lstm_ctx_create: null argument");
   const ppo_lstm_cfg &c = *cfg;
-  PPO_REQUIRE(c.obs_dim > 0 && c.window > 0 && c.act_dim > 0 && c.act_dim <= kMaxA,
+  PPO_REQUIRE(c.obs_dim > 0 && c.window > 0 && c.act_dim > 0 && c.act_dim <= kMaxAct,
               "ppo_lstm_ctx_create: bad obs/window/act (%d, %d, %d)", c.obs_dim, c.window,
               c.act_dim);
   PPO_REQUIRE(c.latent > 0 && c.latent % 4 == 0 && c.latent <= 1024,
@@ -1901,6 +1888,7 @@ extern "C" int ppo_lstm_minibatch_grad(ppo_lstm_ctx *x, const float *states_d,
   if (int rc = check_rows(x, b)) return rc;
   PPO_REQUIRE(b > 0, "ppo_lstm_minibatch_grad: empty minibatch");
   PPO_HIP_TRY(hipSetDevice(x->device));
+  const LossCoef coef{clip_lo, clip_hi, entropy_coef, inv_b, inv_ba};
   TimingScope ts(x);
   hipStream_t st = as_stream(stream);
   const ppo_lstm_cfg &c = x->cfg;
@@ -1925,11 +1913,7 @@ extern "C" int ppo_lstm_minibatch_grad(ppo_lstm_ctx *x, const float *states_d,
   h.dzs = x->dz[1][0];
   h.dv = x->dz[2][0];
   h.row_part = x->row_part;
-  h.clip_lo = clip_lo;
-  h.clip_hi = clip_hi;
-  h.ent_coef = entropy_coef;
-  h.inv_b = inv_b;
-  h.inv_ba = inv_ba;
+  h.coef = coef;
   h.b = b;
   h.a = A;
   launch_k(TimRec{KC_UPDATE_HEAD, "lstm_update_head_kernel", 0.0, 0.0}, lstm_update_head_kernel,
@@ -1937,8 +1921,8 @@ extern "C" int ppo_lstm_minibatch_grad(ppo_lstm_ctx *x, const float *states_d,
   PPO_LAUNCHED();
   if (loss_d) {
     launch_k(TimRec{KC_REDUCE, "lstm_loss_kernel", 0.0, 0.0}, lstm_loss_kernel, dim3(1),
-             dim3(256), 0, st, x->row_part, b, inv_b, inv_ba, entropy_coef * x->ent_log_share,
-             loss_d);
+             dim3(256), 0, st, x->row_part, b, coef.inv_b, coef.inv_ba,
+             logged_ent_coef(coef, x->ent_log_share), loss_d);
     PPO_LAUNCHED();
   }
   {  // critic: MLP, then BiLSTM (the gradient of h at t = W-1 lands in dy[0])

@@ -29,6 +29,7 @@
 #include "conv_lds.h"
 #include "gemm.h"
 #include "gemm_ops.h"
+#include "ppo_loss.h"
 #include "reduce_slabs.h"
 #include "timing.h"
 
@@ -37,7 +38,6 @@ namespace cnn {
 
 using namespace conv;
 
-constexpr int kMaxA = 32;
 constexpr int kMlpSplits = 32;        // split-K slabs of the MLP weight gradients (max)
 constexpr int kConvMaxSplits = 256;   // split-K slabs of a conv weight gradient (max)
 constexpr int kHeadSplits = 256;      // row blocks of the update head (log-std / loss partials)
@@ -77,11 +77,10 @@ struct HeadArgs {
   float *ls_part;        // [splits][A]
   float *loss_part;      // [splits][2]
   int splits;
-  float clip_lo, clip_hi, ent_coef, inv_b, inv_ba;
+  LossCoef coef;
 };
 
-// ppo.py:22-26 per env row (torch formulas of policy_head_kernel): mean = omv * tanh(z);
-// action = eps * std + mean; logp = sum_a (-(x - mu)^2) / (2 var) - log(std) - log(sqrt(2 pi)).
+// ppo.py:22-26 per env row (ppo_loss.h): mean = omv * tanh(z), sampled action, summed log-prob.
 __global__ __launch_bounds__(256) void cnn_policy_head_kernel(HeadArgs q) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= q.b) return;
@@ -95,20 +94,19 @@ __global__ __launch_bounds__(256) void cnn_policy_head_kernel(HeadArgs q) {
     if (!q.action) continue;
     const float sd = expf(q.logstd[k]);
     const float e = q.eps ? q.eps[idx] : philox_normal_at(q.seed, off + idx);
-    const float x = e * sd + mu;  // torch.normal: randn * std, then + mean (two roundings)
+    const float x = normal_sample(e, sd, mu);
     q.action[idx] = x;
-    const float d = x - mu;
-    lp += ((-(d * d)) / (2.f * (sd * sd)) - logf(sd)) - kLogSqrt2Pi;
+    lp += normal_logp_term(x - mu, sd * sd, logf(sd));
   }
   if (q.logp_out) q.logp_out[n] = lp;
   if (q.value_out) q.value_out[n] = q.vc[n];
 }
 
-// ppo.py:108-135 per minibatch row; block s owns rows [s*B/S, (s+1)*B/S) and writes its fixed-
-// order partial sums of d(loss)/d(actor_logstd) and of the two loss terms.
+// ppo.py:108-135 per minibatch row (ppo_loss.h); block s owns rows [s*B/S, (s+1)*B/S) and writes
+// its fixed-order partial sums of d(loss)/d(actor_logstd) and of the two loss terms.
 __global__ __launch_bounds__(256) void cnn_update_head_kernel(HeadArgs q) {
-  __shared__ float s_sd[kMaxA], s_lsd[kMaxA], s_var[kMaxA];
-  __shared__ float red[256][kMaxA + 2];
+  __shared__ float s_sd[kMaxAct], s_lsd[kMaxAct], s_var[kMaxAct];
+  __shared__ float red[256][kMaxAct + 2];
   const int tid = threadIdx.x, A = q.a;
   if (tid < A) {
     const float sd = expf(q.logstd[tid]);
@@ -119,50 +117,38 @@ __global__ __launch_bounds__(256) void cnn_update_head_kernel(HeadArgs q) {
   __syncthreads();
   const int j0 = static_cast<int>((static_cast<int64_t>(blockIdx.x) * q.b) / q.splits);
   const int j1 = static_cast<int>((static_cast<int64_t>(blockIdx.x + 1) * q.b) / q.splits);
-  float ls[kMaxA];
+  float ls[kMaxAct];
 #pragma unroll
-  for (int k = 0; k < kMaxA; ++k) ls[k] = 0.f;
+  for (int k = 0; k < kMaxAct; ++k) ls[k] = 0.f;
   float la = 0.f, lc = 0.f;
   for (int j = j0 + tid; j < j1; j += 256) {
     const int64_t sr = q.rows[j];
     float lp = 0.f;
 #pragma unroll
-    for (int k = 0; k < kMaxA; ++k) {
+    for (int k = 0; k < kMaxAct; ++k) {
       if (k >= A) break;
       const float mu = q.omv * q.ya[static_cast<int64_t>(j) * A + k];
       const float d = q.actions[sr * A + k] - mu;
-      lp += ((-(d * d)) / (2.f * s_var[k]) - s_lsd[k]) - kLogSqrt2Pi;
+      lp += normal_logp_term(d, s_var[k], s_lsd[k]);
     }
-    const float adv = q.adv[sr];
-    const float ratio = expf(lp - q.old_logp[sr]);
-    const float s1 = ratio * adv;
-    const float cl = ratio < q.clip_lo ? q.clip_lo : (ratio > q.clip_hi ? q.clip_hi : ratio);
-    const float s2 = cl * adv;
-    const float mn = (s1 != s1 || s2 != s2) ? (s1 + s2) : (s2 < s1 ? s2 : s1);
-    const float gg = -q.inv_b;
-    const float g1 = (s1 < s2) ? gg : (s1 == s2 ? gg * 0.5f : 0.f);
-    const float g2 = (s2 < s1) ? gg : (s1 == s2 ? gg * 0.5f : 0.f);
-    const bool inside = (ratio >= q.clip_lo) && (ratio <= q.clip_hi);
-    const float dlogp = (g1 * adv + (inside ? g2 * adv : 0.f)) * ratio;
+    const Surrogate sg = clipped_surrogate(lp, q.old_logp[sr], q.adv[sr], q.coef);
 #pragma unroll
-    for (int k = 0; k < kMaxA; ++k) {
+    for (int k = 0; k < kMaxAct; ++k) {
       if (k >= A) break;
       const int64_t idx = static_cast<int64_t>(j) * A + k;
       const float y = q.ya[idx];
       const float d = q.actions[sr * A + k] - q.omv * y;
-      const float dmu = dlogp * (d / s_var[k]);
-      q.dza[idx] = (dmu * q.omv) * (1.f - y * y);
-      ls[k] += dlogp * ((d * d) / s_var[k] - 1.f) - q.ent_coef * q.inv_ba;
+      q.dza[idx] = tanh_mean_grad(sg.dlogp, d, s_var[k], q.omv, y);
+      ls[k] += logstd_grad(sg.dlogp, d, s_var[k], q.coef);
     }
-    la += mn;
+    la += sg.mn;
     const float v = q.vc[j];
     const float diff = v - q.vt[sr];
-    const float ad = fabsf(diff);
-    lc += (ad < 1.f) ? 0.5f * ad * ad : (ad - 0.5f);
-    q.dzc[j] = q.inv_b * (diff < -1.f ? -1.f : (diff > 1.f ? 1.f : diff));
+    lc += huber(diff);
+    q.dzc[j] = huber_grad(diff, q.coef.inv_b);
   }
 #pragma unroll
-  for (int k = 0; k < kMaxA; ++k)
+  for (int k = 0; k < kMaxAct; ++k)
     if (k < A) red[tid][k] = ls[k];
   red[tid][A] = la;
   red[tid][A + 1] = lc;
@@ -213,9 +199,9 @@ __global__ __launch_bounds__(256) void pixel_env_step_kernel(PixelArgs p) {
   const int64_t g = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (g >= static_cast<int64_t>(p.n) * units) return;
   const int n = static_cast<int>(g / units), u = static_cast<int>(g % units);
-  int qa[kMaxA];
+  int qa[kMaxAct];
 #pragma unroll
-  for (int j = 0; j < kMaxA; ++j) {
+  for (int j = 0; j < kMaxAct; ++j) {
     qa[j] = 0;
     if (j < p.a && p.action) {
       const float f = floorf(p.action[static_cast<int64_t>(n) * p.a + j] * 8.f);
@@ -232,7 +218,7 @@ __global__ __launch_bounds__(256) void pixel_env_step_kernel(PixelArgs p) {
     int j = (2 * ch + ((x + y) & 1)) % p.a;
     int qv = 0;
 #pragma unroll
-    for (int k = 0; k < kMaxA; ++k)
+    for (int k = 0; k < kMaxAct; ++k)
       if (k == j) qv = qa[k];
     word |= ((hsh + static_cast<uint32_t>(qv)) & 255u) << (8 * e);
   }
@@ -832,7 +818,7 @@ extern "C" int ppo_cnn_ctx_create(const ppo_cnn_cfg *cfg, int device, ppo_cnn_ct
   PPO_REQUIRE(c.height == L1::hin && c.width == L1::win && c.channels == L1::cin,
               "ppo_cnn_ctx_create: frames %dx%dx%d; the compiled encoder takes %dx%dx%d",
               c.height, c.width, c.channels, L1::hin, L1::win, L1::cin);
-  PPO_REQUIRE(c.act_dim >= 1 && c.act_dim <= kMaxA, "ppo_cnn_ctx_create: act_dim %d", c.act_dim);
+  PPO_REQUIRE(c.act_dim >= 1 && c.act_dim <= kMaxAct, "ppo_cnn_ctx_create: act_dim %d", c.act_dim);
   PPO_REQUIRE(c.n_hidden >= 0 && c.n_hidden <= PPO_MAX_LAYERS, "ppo_cnn_ctx_create: %d hidden layers",
               c.n_hidden);
   PPO_REQUIRE(c.activation >= PPO_ACT_RELU && c.activation <= PPO_ACT_ELU,
@@ -1063,6 +1049,7 @@ extern "C" int ppo_cnn_minibatch_grad(ppo_cnn_ctx *x, const uint8_t *frames_d,
               "ppo_cnn_minibatch_grad: null argument");
   PPO_REQUIRE(b > 0, "ppo_cnn_minibatch_grad: empty minibatch");
   PPO_HIP_TRY(hipSetDevice(x->device));
+  const LossCoef coef{clip_lo, clip_hi, entropy_coef, inv_b, inv_ba};
   hipStream_t st = as_stream(stream);
   TimingScope ts(x);
   const int A = x->cfg.act_dim;
@@ -1085,11 +1072,7 @@ extern "C" int ppo_cnn_minibatch_grad(ppo_cnn_ctx *x, const uint8_t *frames_d,
   h.ls_part = x->ls_part;
   h.loss_part = x->loss_part;
   h.splits = head_splits;
-  h.clip_lo = clip_lo;
-  h.clip_hi = clip_hi;
-  h.ent_coef = entropy_coef;
-  h.inv_b = inv_b;
-  h.inv_ba = inv_ba;
+  h.coef = coef;
   launch_k(TimRec{KC_UPDATE_HEAD, "cnn_update_head_kernel", 0.0, 0.0}, cnn_update_head_kernel,
            dim3(head_splits), dim3(256), 0, st, h);
   PPO_LAUNCHED();
@@ -1131,10 +1114,10 @@ extern "C" int ppo_cnn_minibatch_grad(ppo_cnn_ctx *x, const uint8_t *frames_d,
   r.grad = grad_d;
   r.loss_part = x->loss_part;
   r.loss_splits = head_splits;
-  r.inv_b = inv_b;
+  r.inv_b = coef.inv_b;
   r.logstd = x->params + x->logstd_off;
   r.act_dim = A;
-  r.ent_coef = entropy_coef * x->ent_log_share;
+  r.ent_coef = logged_ent_coef(coef, x->ent_log_share);
   r.loss_out = loss_d;
   launch_k(TimRec{KC_REDUCE, "reduce_slabs_kernel", 0.0, 0.0}, cnn_reduce_kernel,
            dim3(ceil_div(x->total, kRedParams)), dim3(kRedThreads), 0, st, r);
@@ -1159,7 +1142,7 @@ extern "C" int ppo_synthetic_pixel_step(uint32_t seed, int t, const float *actio
                                         const float *base_reward_d, const uint8_t *base_term_d,
                                         double *reward_out_d, uint8_t *term_out_d, void *stream) {
   PPO_REQUIRE(frames_out_d != nullptr, "ppo_synthetic_pixel_step: null frames");
-  PPO_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0 && (h * w * c) % 4 == 0 && a >= 1 && a <= kMaxA,
+  PPO_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0 && (h * w * c) % 4 == 0 && a >= 1 && a <= kMaxAct,
               "ppo_synthetic_pixel_step: bad shape");
   PPO_REQUIRE(!reward_out_d || (base_reward_d && base_term_d && term_out_d && action_d && t >= 1),
               "ppo_synthetic_pixel_step: rewards need the base streams, an action and t >= 1");

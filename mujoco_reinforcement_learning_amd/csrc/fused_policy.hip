@@ -290,11 +290,10 @@ __device__ __forceinline__ void policy_body(const PolicyFusedArgs &q, const Fuse
           const float mu = q.omv * tanhf(zz);
           const int64_t idx = static_cast<int64_t>(env) * A + n;
           const float e = eps_s[(env - row0) * 8 + n];  // staged in the prologue
-          const float x = e * sd + mu;  // torch.normal: randn*std then + mean (two roundings)
+          const float x = normal_sample(e, sd, mu);
           if (q.action) q.action[idx] = x;
           if (q.mean) q.mean[idx] = mu;
-          const float d = x - mu;
-          lp = ((-(d * d)) * i2var - lsd) - kLogSqrt2Pi;
+          lp = normal_logp_term_rcp(x - mu, i2var, lsd);
         }
         // Normal.log_prob(...).sum(1): fixed xor tree over the 16 head lanes (pads are 0), the
         // same tree as the update kernel's loss head

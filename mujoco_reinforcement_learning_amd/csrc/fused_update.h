@@ -7,6 +7,7 @@
 
 #include <cstdint>
 
+#include "ppo_loss.h"
 #include "reduce_slabs.h"
 #include "timing.h"
 
@@ -107,7 +108,8 @@ struct FusedArgs {
   bool direct;
   bool pack_w;                 // prep also refreshes the bf16 weight images from the masters
   int b, din, act_dim, act, hidden;
-  float omv, clip_lo, clip_hi, ent_coef, inv_b, inv_ba;
+  float omv;
+  LossCoef coef;
   float *slabs;                // (G, slab_stride) partial gradients in the flat layout
   int64_t slab_stride;
   float *loss_part;            // (G, 2): actor / critic loss-term sums per workgroup

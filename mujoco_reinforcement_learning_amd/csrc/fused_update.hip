@@ -760,33 +760,23 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
             const float mu = q.omv * y;
             const float x = valid[i] ? xs[i] : mu;
             d = x - mu;
-            lp = ((-(d * d)) * (0.5f * h_ivar) - h_lsd) - kLogSqrt2Pi;  // 0.5/var: exact scaling
+            lp = normal_logp_term_rcp(d, 0.5f * h_ivar, h_lsd);  // 0.5/var: exact scaling
           }
           // Normal.log_prob(...).sum(1): fixed xor tree over the 16 head lanes (pads are 0), the
           // same tree as the rollout's policy kernel
           const float logp = row16_sum(lp);
           const float old_lp = valid[i] ? olp[i] : logp;
           const float adv = valid[i] ? advs[i] : 0.f;
-          const float ratio = expf(logp - old_lp);
-          const float s1 = ratio * adv;
-          const float cl = ratio < q.clip_lo ? q.clip_lo : (ratio > q.clip_hi ? q.clip_hi : ratio);
-          const float s2 = cl * adv;
-          const float mn = (s1 != s1 || s2 != s2) ? (s1 + s2) : (s2 < s1 ? s2 : s1);
-          const float gg = -q.inv_b;
-          const float g1 = (s1 < s2) ? gg : (s1 == s2 ? gg * 0.5f : 0.f);
-          const float g2 = (s2 < s1) ? gg : (s1 == s2 ? gg * 0.5f : 0.f);
-          const bool inside = (ratio >= q.clip_lo) && (ratio <= q.clip_hi);
-          const float dratio = g1 * adv + (inside ? g2 * adv : 0.f);
-          const float dlogp = valid[i] ? dratio * ratio : 0.f;
+          const Surrogate sg = clipped_surrogate(logp, old_lp, adv, q.coef);
+          const float dlogp = valid[i] ? sg.dlogp : 0.f;
           if (act_lane) {
-            const float dmu = dlogp * (d * h_ivar);
-            dz[i] = (dmu * q.omv) * (1.f - y * y);
+            dz[i] = tanh_mean_grad_rcp(dlogp, d, h_ivar, q.omv, y);
             if (valid[i]) {
-              g_ls += dlogp * ((d * d) * h_ivar - 1.f) - q.ent_coef * q.inv_ba;
+              g_ls += logstd_grad_rcp(dlogp, d, h_ivar, q.coef);
               g_bh += dz[i];
             }
           }
-          if (valid[i] && n == 0) g_loss += mn;
+          if (valid[i] && n == 0) g_loss += sg.mn;
         }
       } else {
 #pragma unroll
@@ -794,10 +784,8 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
           const float v = N.bh ? zr[i] + h_b : zr[i];
           const float vt = valid[i] ? vts[i] : v;
           const float diff = v - vt;
-          const float ad = fabsf(diff);
-          const float hl = (ad < 1.f) ? 0.5f * ad * ad : (ad - 0.5f);
-          g_loss = (valid[i] && n == 0) ? g_loss + hl : g_loss;
-          dz[i] = n == 0 ? q.inv_b * (diff < -1.f ? -1.f : (diff > 1.f ? 1.f : diff)) : 0.f;
+          g_loss = (valid[i] && n == 0) ? g_loss + huber(diff) : g_loss;
+          dz[i] = n == 0 ? huber_grad(diff, q.coef.inv_b) : 0.f;
           g_bh = n == 0 ? g_bh + dz[i] : g_bh;
         }
       }

@@ -33,6 +33,7 @@
 #include "fused_update.h"
 #include "gemm.h"
 #include "gemm_ops.h"
+#include "ppo_loss.h"
 #include "reduce_slabs.h"
 #include "timing.h"
 #include "wide_path.h"
@@ -42,8 +43,6 @@ namespace ppo {
 // ============================================================================================
 // Heads
 // ============================================================================================
-constexpr int kMaxAct = 32;
-
 struct PolicyHeadArgs {
   const float *ha;   // actor last hidden (n, da) or null
   const float *hc;   // critic last hidden (n, dc) or null
@@ -58,8 +57,7 @@ struct PolicyHeadArgs {
   int bf16;                       // precision bf16: head operands rounded to bf16 (f32 accumulate)
 };
 
-// One wave per env row.  logp follows Normal.log_prob term by term:
-//   (-(x-mu)^2) / (2*var) - log(std) - log(sqrt(2*pi)),  var = std*std,  summed a = 0..A-1.
+// One wave per env row.  Sampling and log-prob: ppo_loss.h, summed a = 0..A-1.
 template <int HPL>
 __global__ __launch_bounds__(256) void policy_head_kernel(PolicyHeadArgs q) {
   const int lane = threadIdx.x & 63;
@@ -95,12 +93,10 @@ __global__ __launch_bounds__(256) void policy_head_kernel(PolicyHeadArgs q) {
       const float e =
           q.eps ? q.eps[idx]
                 : philox_normal_at(q.seed, q.offset + (q.offset_base ? *q.offset_base : 0) + idx);
-      const float x = e * sd + mu;  // torch.normal: randn*std then + mean (two roundings)
+      const float x = normal_sample(e, sd, mu);
       if (q.action) q.action[idx] = x;
       if (q.mean) q.mean[idx] = mu;
-      const float d = x - mu;
-      const float var = sd * sd;
-      lp = ((-(d * d)) / (2.f * var) - logf(sd)) - kLogSqrt2Pi;
+      lp = normal_logp_term(x - mu, sd * sd, logf(sd));
     }
     if (q.logp) {
       float s = 0.f;
@@ -133,7 +129,7 @@ struct UpdateHeadArgs {
   int rows_max;
   const int32_t *rows_n;         // device count (nullable)
   const float *actions, *old_logp, *adv, *vtarget;  // storage arrays
-  float clip_lo, clip_hi, ent_coef, inv_b, inv_ba;
+  LossCoef coef;
   float *logstd_part;            // (splits, A)
   float *loss_part;              // (splits, 2): sum over rows of actor / critic loss terms
   int splits;
@@ -156,7 +152,7 @@ __device__ __forceinline__ float4 rb4(float4 v, int bf16) {
 // 16t + 4qd of its row; a head dot product is NJ float4 FMAs against LDS-staged head weights
 // (same address for the 16 rows -> LDS broadcast) plus a 2-step shuffle over the row's 4 lanes.
 // Per-action work (tanh, log-prob, dz) is spread over the 4 lanes: lane qd owns actions
-// a = 4k + qd.  Same torch formulas as update_head_kernel below.
+// a = 4k + qd.  The formulas are ppo_loss.h's.
 // FW (A <= kFusedHeadAct): also accumulate the head layer's weight gradient, dW = dz^T H_L and
 // db = sum dz per net, over the block's rows while H_L is hot in L1/L2 -- lane owns float4
 // column chunk c = lane + 64u of both nets -- so the split-K head GEMM (a second full read of
@@ -247,7 +243,7 @@ __global__ __launch_bounds__(256, NJ <= 16 ? 2 : 1) void update_head_q4_kernel(U
         const float x = valid ? q.actions[sr * A + a] : mu;
         const float d = x - mu;
         const float var = sd * sd;
-        lp_row[a] = ((-(d * d)) / (2.f * var) - logf(sd)) - kLogSqrt2Pi;
+        lp_row[a] = normal_logp_term(d, var, logf(sd));
         yk[k] = y, dk[k] = d, vk[k] = var;
       }
     }
@@ -256,27 +252,17 @@ __global__ __launch_bounds__(256, NJ <= 16 ? 2 : 1) void update_head_q4_kernel(U
     for (int a = 0; a < A; ++a) logp += lp_row[a];
     const float old_lp = valid ? q.old_logp[sr] : logp;
     const float adv = valid ? q.adv[sr] : 0.f;
-    const float ratio = expf(logp - old_lp);
-    const float s1 = ratio * adv;
-    const float cl = ratio < q.clip_lo ? q.clip_lo : (ratio > q.clip_hi ? q.clip_hi : ratio);
-    const float s2 = cl * adv;
-    const float mn = (s1 != s1 || s2 != s2) ? (s1 + s2) : (s2 < s1 ? s2 : s1);
-    const float g = -q.inv_b;
-    const float g1 = (s1 < s2) ? g : (s1 == s2 ? g * 0.5f : 0.f);
-    const float g2 = (s2 < s1) ? g : (s1 == s2 ? g * 0.5f : 0.f);
-    const bool inside = (ratio >= q.clip_lo) && (ratio <= q.clip_hi);
-    const float dratio = g1 * adv + (inside ? g2 * adv : 0.f);
-    const float dlogp = valid ? dratio * ratio : 0.f;
-    if (valid && qd == 0) la_acc += mn;
+    const Surrogate sg = clipped_surrogate(logp, old_lp, adv, q.coef);
+    const float dlogp = valid ? sg.dlogp : 0.f;
+    if (valid && qd == 0) la_acc += sg.mn;
 #pragma unroll
     for (int k = 0; k < KA; ++k) {
       const int a = 4 * k + qd;
       if (a < A) {
-        const float dmu = dlogp * (dk[k] / vk[k]);
-        const float dz = (dmu * q.omv) * (1.f - yk[k] * yk[k]);
+        const float dz = tanh_mean_grad(dlogp, dk[k], vk[k], q.omv, yk[k]);
         dz_row[a] = dz;
         if (valid) {
-          ls_acc[k] += dlogp * ((dk[k] * dk[k]) / vk[k] - 1.f) - q.ent_coef * q.inv_ba;
+          ls_acc[k] += logstd_grad(dlogp, dk[k], vk[k], q.coef);
           q.dza[static_cast<int64_t>(j) * A + a] = dz;
         }
       }
@@ -319,9 +305,8 @@ __global__ __launch_bounds__(256, NJ <= 16 ? 2 : 1) void update_head_q4_kernel(U
     const float v = q.bc ? p + q.bc[0] : p;
     const float vt = valid ? q.vtarget[sr] : v;
     const float diff = v - vt;
-    const float ad = fabsf(diff);
-    if (valid && qd == 0) lc_acc += (ad < 1.f) ? 0.5f * ad * ad : (ad - 0.5f);
-    const float dv = q.inv_b * (diff < -1.f ? -1.f : (diff > 1.f ? 1.f : diff));
+    if (valid && qd == 0) lc_acc += huber(diff);
+    const float dv = huber_grad(diff, q.coef.inv_b);
     if (valid && qd == 0) q.dzc[j] = dv;
     float4 *gcrow = reinterpret_cast<float4 *>(q.gc + static_cast<int64_t>(j) * D);
     const float dvb = rb(dv, q.bf16);
@@ -442,9 +427,7 @@ __global__ __launch_bounds__(256, NJ <= 16 ? 2 : 1) void update_head_q4_kernel(U
   }
 }
 
-// Generic head (any widths): one wave per row.  Gradients follow torch's autograd formulas:
-// minimum() splits a tie's gradient in halves, clamp passes it on the closed interval,
-// huber_loss_backward clips at +-delta, tanh backward is grad*(1-y*y).
+// Generic head (any widths): one wave per row.  The formulas are ppo_loss.h's.
 template <int HPL>
 __global__ __launch_bounds__(256) void update_head_kernel(UpdateHeadArgs q) {
   __shared__ float red[4][kMaxAct + 2];
@@ -487,30 +470,18 @@ __global__ __launch_bounds__(256) void update_head_kernel(UpdateHeadArgs q) {
       const float x = q.actions[sr * A + lane];
       d = x - mu;
       var = sd * sd;
-      lp = ((-(d * d)) / (2.f * var) - logf(sd)) - kLogSqrt2Pi;
+      lp = normal_logp_term(d, var, logf(sd));
     }
     float logp = 0.f;
     for (int a = 0; a < A; ++a) logp += __shfl(lp, a, 64);
-    const float ratio = expf(logp - q.old_logp[sr]);
-    const float adv = q.adv[sr];
-    const float s1 = ratio * adv;
-    const float cl = ratio < q.clip_lo ? q.clip_lo : (ratio > q.clip_hi ? q.clip_hi : ratio);
-    const float s2 = cl * adv;
-    const float mn = (s1 != s1 || s2 != s2) ? (s1 + s2) : (s2 < s1 ? s2 : s1);
-    const float g = -q.inv_b;
-    const float g1 = (s1 < s2) ? g : (s1 == s2 ? g * 0.5f : 0.f);
-    const float g2 = (s2 < s1) ? g : (s1 == s2 ? g * 0.5f : 0.f);
-    const bool inside = (ratio >= q.clip_lo) && (ratio <= q.clip_hi);
-    const float dratio = g1 * adv + (inside ? g2 * adv : 0.f);
-    const float dlogp = dratio * ratio;
+    const Surrogate sg = clipped_surrogate(logp, q.old_logp[sr], q.adv[sr], q.coef);
     float dz = 0.f;
     if (lane < A) {
-      const float dmu = dlogp * (d / var);
-      dz = (dmu * q.omv) * (1.f - y * y);
-      lsacc += dlogp * ((d * d) / var - 1.f) - q.ent_coef * q.inv_ba;
+      dz = tanh_mean_grad(sg.dlogp, d, var, q.omv, y);
+      lsacc += logstd_grad(sg.dlogp, d, var, q.coef);
       q.dza[static_cast<int64_t>(j) * A + lane] = dz;
     }
-    if (lane == 0) la_acc += mn;
+    if (lane == 0) la_acc += sg.mn;
     // dH_L(actor) = (dz . W_head) * act'(h)
     float *gr = q.ga + static_cast<int64_t>(j) * q.da;
 #pragma unroll
@@ -539,9 +510,8 @@ __global__ __launch_bounds__(256) void update_head_kernel(UpdateHeadArgs q) {
     float v = wave_sum(part);
     if (q.bc) v = v + q.bc[0];
     const float diff = v - q.vtarget[sr];
-    const float ad = fabsf(diff);
-    if (lane == 0) lc_acc += (ad < 1.f) ? 0.5f * ad * ad : (ad - 0.5f);
-    const float dv = q.inv_b * (diff < -1.f ? -1.f : (diff > 1.f ? 1.f : diff));
+    if (lane == 0) lc_acc += huber(diff);
+    const float dv = huber_grad(diff, q.coef.inv_b);
     if (lane == 0) q.dzc[j] = dv;
     float *gc = q.gc + static_cast<int64_t>(j) * q.dc;
 #pragma unroll
@@ -728,9 +698,8 @@ static bool fused_active(const ppo_ctx *ctx) {
 // slab reduction.  Same contract as the layered path below.
 static FusedArgs fused_args(ppo_ctx *ctx, const float *states_d, const float *actions_d,
                             const float *old_logp_d, const float *adv_d, const float *vtarget_d,
-                            const int32_t *rows_d, int b, const int32_t *count_d, float clip_lo,
-                            float clip_hi, float entropy_coef, float inv_b, float inv_ba,
-                            bool staged, bool pack_w) {
+                            const int32_t *rows_d, int b, const int32_t *count_d,
+                            const LossCoef &coef, bool staged, bool pack_w) {
   FusedArgs q{};
   fused_nets(ctx, q.net);
   q.logstd = ctx->params + ctx->net[0].logstd_off;
@@ -753,11 +722,7 @@ static FusedArgs fused_args(ppo_ctx *ctx, const float *states_d, const float *ac
   q.act = ctx->cfg.activation;
   q.hidden = ctx->fused_hidden;
   q.omv = ctx->cfg.output_max_value;
-  q.clip_lo = clip_lo;
-  q.clip_hi = clip_hi;
-  q.ent_coef = entropy_coef;
-  q.inv_b = inv_b;
-  q.inv_ba = inv_ba;
+  q.coef = coef;
   q.slabs = ctx->fslabs;
   q.slab_stride = ctx->total_params;
   q.loss_part = ctx->floss;
@@ -848,10 +813,10 @@ static ReduceArgs fused_reduce_args(const ppo_ctx *ctx, const FusedArgs &q, floa
   r.grad = grad_d;
   r.loss_part = ctx->floss;
   r.loss_splits = q.G;
-  r.inv_b = q.inv_b;
+  r.inv_b = q.coef.inv_b;
   r.logstd = ctx->params + ctx->net[0].logstd_off;
   r.act_dim = A;
-  r.ent_coef = q.ent_coef * ctx->ent_log_share;
+  r.ent_coef = logged_ent_coef(q.coef, ctx->ent_log_share);
   r.loss_out = loss_d;
   return r;
 }
@@ -859,13 +824,11 @@ static ReduceArgs fused_reduce_args(const ppo_ctx *ctx, const FusedArgs &q, floa
 static int fused_minibatch_grad(ppo_ctx *ctx, const float *states_d, const float *actions_d,
                                 const float *old_logp_d, const float *adv_d,
                                 const float *vtarget_d, const int32_t *rows_d, int b,
-                                const int32_t *count_d, float clip_lo, float clip_hi,
-                                float entropy_coef, float inv_b, float inv_ba, float *grad_d,
+                                const int32_t *count_d, const LossCoef &coef, float *grad_d,
                                 float *loss_d, hipStream_t st, bool staged = false,
                                 bool pack_w = true, bool gathered = false) {
   const FusedArgs q = fused_args(ctx, states_d, actions_d, old_logp_d, adv_d, vtarget_d, rows_d,
-                                 b, count_d, clip_lo, clip_hi, entropy_coef, inv_b, inv_ba,
-                                 staged, pack_w);
+                                 b, count_d, coef, staged, pack_w);
   gathered = gathered && staged && gathered_holds(ctx, rows_d, b);
   if ((!gathered && !q.direct) || pack_w) {
     FusedArgs p = q;
@@ -1327,8 +1290,8 @@ extern "C" int ppo_minibatch_grad_staged(ppo_ctx *ctx, const int32_t *rows_d, in
               "ppo_minibatch_grad_staged: pre-gathered rows take no device count");
   TimingScope timing_scope(ctx);
   return fused_minibatch_grad(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, rows_d, b,
-                              count_d, clip_lo, clip_hi, entropy_coef, inv_b, inv_ba, grad_d,
-                              loss_d, as_stream(stream), true,
+                              count_d, LossCoef{clip_lo, clip_hi, entropy_coef, inv_b, inv_ba},
+                              grad_d, loss_d, as_stream(stream), true,
                               (flags & PPO_STAGED_WEIGHTS_CURRENT) == 0,
                               (flags & PPO_STAGED_ROWS_GATHERED) != 0);
 }
@@ -1355,8 +1318,8 @@ extern "C" int ppo_adam_pack_gather(ppo_ctx *ctx, const float *g_d, float *m_d, 
   t.srow = ctx->fsrow;
   // direct: the next fused launch reads its rows through the indices, nothing to gather
   const bool direct = next_b > 0 && fused_args(ctx, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                               next_rows_d, next_b, nullptr, 0.f, 0.f, 0.f, 0.f,
-                                               0.f, true, false).direct;
+                                               next_rows_d, next_b, nullptr, LossCoef{}, true,
+                                               false).direct;
   t.b = direct ? 0 : next_b;
   t.reduce = false;
   ReduceArgs r{};
@@ -1381,7 +1344,7 @@ extern "C" int ppo_gather_staged_rows(ppo_ctx *ctx, const int32_t *rows_d, int b
               "ppo_gather_staged_rows: b=%d outside [1, max_rows=%d]", b, ctx->cfg.max_rows);
   TimingScope timing_scope(ctx);
   const FusedArgs q = fused_args(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, rows_d, b,
-                                 nullptr, 0.f, 0.f, 0.f, 0.f, 0.f, true, false);
+                                 nullptr, LossCoef{}, true, false);
   if (int rc = fused_prep(ctx, q, as_stream(stream))) return rc;
   note_gathered(ctx, rows_d, b);
   return 0;
@@ -1427,7 +1390,7 @@ extern "C" int ppo_update_step_staged(ppo_ctx *ctx, const int32_t *rows_d, int b
   const bool gathered = (flags & PPO_STAGED_ROWS_GATHERED) && gathered_holds(ctx, rows_d, b);
   const bool current = flags & PPO_STAGED_WEIGHTS_CURRENT;
   FusedArgs q = fused_args(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, rows_d, b, nullptr,
-                           clip_lo, clip_hi, entropy_coef, inv_b, inv_ba, true, !current);
+                           LossCoef{clip_lo, clip_hi, entropy_coef, inv_b, inv_ba}, true, !current);
   if ((!gathered && !q.direct) || !current) {
     FusedArgs p = q;
     p.b = (gathered || q.direct) ? 0 : b;
@@ -1562,16 +1525,15 @@ extern "C" int ppo_minibatch_grad(ppo_ctx *ctx, const float *states_d, const flo
               "ppo_minibatch_grad: null buffer");
   PPO_REQUIRE(b > 0 && b <= ctx->cfg.max_rows, "ppo_minibatch_grad: b=%d outside [1, max_rows=%d]",
               b, ctx->cfg.max_rows);
+  const LossCoef coef{clip_lo, clip_hi, entropy_coef, inv_b, inv_ba};
   hipStream_t st = as_stream(stream);
   TimingScope timing_scope(ctx);
   if (fused_active(ctx))
     return fused_minibatch_grad(ctx, states_d, actions_d, old_logp_d, adv_d, vtarget_d, rows_d, b,
-                                count_d, clip_lo, clip_hi, entropy_coef, inv_b, inv_ba, grad_d,
-                                loss_d, st);
+                                count_d, coef, grad_d, loss_d, st);
   if (wide_active(ctx))
     return wide_minibatch_grad(ctx, states_d, actions_d, old_logp_d, adv_d, vtarget_d, rows_d, b,
-                               count_d, clip_lo, clip_hi, entropy_coef, inv_b, inv_ba, grad_d,
-                               loss_d, st);
+                               count_d, coef, grad_d, loss_d, st);
   const bool both[2] = {true, true};
   const int din = ctx->cfg.obs_dim * ctx->cfg.window;
   const int A = ctx->cfg.act_dim;
@@ -1609,11 +1571,7 @@ extern "C" int ppo_minibatch_grad(ppo_ctx *ctx, const float *states_d, const flo
   u.old_logp = old_logp_d;
   u.adv = adv_d;
   u.vtarget = vtarget_d;
-  u.clip_lo = clip_lo;
-  u.clip_hi = clip_hi;
-  u.ent_coef = entropy_coef;
-  u.inv_b = inv_b;
-  u.inv_ba = inv_ba;
+  u.coef = coef;
   u.logstd_part = ctx->head_part;
   u.loss_part = ctx->head_part + static_cast<int64_t>(kHeadSplits) * A;
   u.splits = head_splits;
@@ -1793,10 +1751,10 @@ extern "C" int ppo_minibatch_grad(ppo_ctx *ctx, const float *states_d, const flo
   r.grad = grad_d;
   r.loss_part = u.loss_part;
   r.loss_splits = head_splits;
-  r.inv_b = inv_b;
+  r.inv_b = coef.inv_b;
   r.logstd = ctx->params + NA.logstd_off;
   r.act_dim = A;
-  r.ent_coef = entropy_coef * ctx->ent_log_share;
+  r.ent_coef = logged_ent_coef(coef, ctx->ent_log_share);
   r.loss_out = loss_d;
   launch_k(TimRec{KC_REDUCE, "reduce_slabs_kernel", static_cast<double>(splits) * P,
                   4.0 * (static_cast<double>(splits) + 1) * P},

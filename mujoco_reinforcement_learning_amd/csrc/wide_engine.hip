@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "fused_common.h"
+#include "ppo_loss.h"
 #include "reduce_slabs.h"
 #include "timing.h"
 #include "wide_gemm.h"
@@ -564,12 +565,10 @@ __global__ __launch_bounds__(256) void wide_policy_head_kernel(WidePolicyArgs q)
       const int64_t idx = static_cast<int64_t>(j) * q.act_dim + a;
       const uint64_t base = q.offset + (q.offset_base ? *q.offset_base : 0);
       const float e = q.eps ? q.eps[idx] : philox_normal_at(q.seed, base + idx);
-      const float x = e * sd + mu;  // torch.normal: randn*std then + mean (two roundings)
+      const float x = normal_sample(e, sd, mu);
       if (q.action) q.action[idx] = x;
       if (q.mean) q.mean[idx] = mu;
-      const float d = x - mu;
-      const float var = sd * sd;
-      lp = ((-(d * d)) / (2.f * var) - logf(sd)) - kLogSqrt2Pi;
+      lp = normal_logp_term(x - mu, sd * sd, logf(sd));
     }
     // the row's log-prob in action order (policy_head_kernel's sequential sum); a fixed trip
     // count so the 32 cross-lane reads issue back to back instead of one round trip per action
@@ -945,12 +944,10 @@ __global__ __launch_bounds__(512) void wide_policy_fused_kernel(WideFusedArgs q)
         const float sd = expf(q.logstd[a]);
         const int64_t idx = static_cast<int64_t>(j) * A + a;
         const float e = q.eps ? q.eps[idx] : philox_normal_at(q.seed, base + idx);
-        const float x = e * sd + mu;  // torch.normal: randn*std then + mean (two roundings)
+        const float x = normal_sample(e, sd, mu);
         if (q.action) q.action[idx] = x;
         if (q.mean) q.mean[idx] = mu;
-        const float d = x - mu;
-        const float var = sd * sd;
-        lp = ((-(d * d)) / (2.f * var) - logf(sd)) - kLogSqrt2Pi;
+        lp = normal_logp_term(x - mu, sd * sd, logf(sd));
       }
       lpt[row][a] = lp;
     }
@@ -1167,7 +1164,7 @@ int wide_policy_step(ppo_ctx *ctx, const float *state_d, int n, const float *eps
 }
 
 // ============================================================================================
-// Minibatch loss heads (update_head_kernel's formulas, ppo.py:109-135): one thread per row.
+// Minibatch loss heads (ppo_loss.h's formulas): one thread per row.
 // dz rows (bf16, 64 columns, zero past the head width and for rows >= count), and per block the
 // fixed-order sums of d loss / d logstd, the head-bias gradients (the f32 dz before rounding) and
 // the two loss terms.
@@ -1182,7 +1179,7 @@ struct WideLossArgs {
   const int32_t *rows_n;
   int b;
   const float *actions, *old_logp, *adv, *vtarget;
-  float clip_lo, clip_hi, ent_coef, inv_b, inv_ba;
+  LossCoef coef;
   float *part, *loss_part;
 };
 
@@ -1222,24 +1219,14 @@ __global__ __launch_bounds__(256) void wide_loss_kernel(WideLossArgs q) {
   const float mu = q.omv * y;
   const float x = (valid && act) ? q.actions[sr * A + a] : mu;
   const float d = x - mu;
-  const float logp = half_sum32(act ? ((-(d * d)) / (2.f * var) - s_logsd[a]) - kLogSqrt2Pi : 0.f);
+  const float logp = half_sum32(act ? normal_logp_term(d, var, s_logsd[a]) : 0.f);
   const float old_lp = valid ? q.old_logp[sr] : logp;
   const float adv = valid ? q.adv[sr] : 0.f;
-  const float ratio = expf(logp - old_lp);
-  const float s1 = ratio * adv;
-  const float cl = ratio < q.clip_lo ? q.clip_lo : (ratio > q.clip_hi ? q.clip_hi : ratio);
-  const float s2 = cl * adv;
-  const float mn = (s1 != s1 || s2 != s2) ? (s1 + s2) : (s2 < s1 ? s2 : s1);
-  const float g = -q.inv_b;
-  const float g1 = (s1 < s2) ? g : (s1 == s2 ? g * 0.5f : 0.f);
-  const float g2 = (s2 < s1) ? g : (s1 == s2 ? g * 0.5f : 0.f);
-  const bool inside = (ratio >= q.clip_lo) && (ratio <= q.clip_hi);
-  const float dratio = g1 * adv + (inside ? g2 * adv : 0.f);
-  const float dlogp = valid ? dratio * ratio : 0.f;
+  const Surrogate sg = clipped_surrogate(logp, old_lp, adv, q.coef);
+  const float dlogp = valid ? sg.dlogp : 0.f;
   const bool live = valid && act;
-  const float dmu = dlogp * (d / var);
-  const float dz = live ? (dmu * q.omv) * (1.f - y * y) : 0.f;
-  const float ls = live ? dlogp * ((d * d) / var - 1.f) - q.ent_coef * q.inv_ba : 0.f;
+  const float dz = live ? tanh_mean_grad(dlogp, d, var, q.omv, y) : 0.f;
+  const float ls = live ? logstd_grad(dlogp, d, var, q.coef) : 0.f;
   // dz row: column pairs (a, a + 1) packed by the even lane (columns >= A are zero)
   const float dz_next = fu::dpp_f<fu::kDppXor1>(dz);
   if ((a & 1) == 0)
@@ -1251,12 +1238,11 @@ __global__ __launch_bounds__(256) void wide_loss_kernel(WideLossArgs q) {
     const float v = q.bc ? zc0 + q.bc[0] : zc0;
     const float vt = valid ? q.vtarget[sr] : v;
     const float diff = v - vt;
-    const float ad = fabsf(diff);
-    const float dv = valid ? q.inv_b * (diff < -1.f ? -1.f : (diff > 1.f ? 1.f : diff)) : 0.f;
+    const float dv = valid ? huber_grad(diff, q.coef.inv_b) : 0.f;
     reinterpret_cast<uint32_t *>(q.dzc + static_cast<int64_t>(j) * 64)[0] = wide::pack2(dv, 0.f);
     rrow[r][0] = dv;
-    rrow[r][1] = valid ? mn : 0.f;
-    rrow[r][2] = valid ? ((ad < 1.f) ? 0.5f * ad * ad : (ad - 0.5f)) : 0.f;
+    rrow[r][1] = valid ? sg.mn : 0.f;
+    rrow[r][2] = valid ? huber(diff) : 0.f;
   }
   __syncthreads();
   float *part = q.part + static_cast<int64_t>(blockIdx.x) * kWidePart;
@@ -1418,8 +1404,7 @@ __global__ __launch_bounds__(kRedThreads) void wide_reduce_kernel(ReduceArgs q, 
 
 int wide_minibatch_grad(ppo_ctx *ctx, const float *states_d, const float *actions_d,
                         const float *old_logp_d, const float *adv_d, const float *vtarget_d,
-                        const int32_t *rows_d, int b, const int32_t *count_d, float clip_lo,
-                        float clip_hi, float entropy_coef, float inv_b, float inv_ba,
+                        const int32_t *rows_d, int b, const int32_t *count_d, const LossCoef &coef,
                         float *grad_d, float *loss_d, hipStream_t st) {
   WideWork &W = *ctx->wide;
   const int rows_pad = static_cast<int>(rup(b, 64));
@@ -1458,11 +1443,7 @@ int wide_minibatch_grad(ppo_ctx *ctx, const float *states_d, const float *action
     q.old_logp = old_logp_d;
     q.adv = adv_d;
     q.vtarget = vtarget_d;
-    q.clip_lo = clip_lo;
-    q.clip_hi = clip_hi;
-    q.ent_coef = entropy_coef;
-    q.inv_b = inv_b;
-    q.inv_ba = inv_ba;
+    q.coef = coef;
     q.part = W.part;
     q.loss_part = W.loss_part;
     launch_k(TimRec{KC_UPDATE_HEAD, "wide_loss_kernel", 0.0,
@@ -1594,10 +1575,10 @@ int wide_minibatch_grad(ppo_ctx *ctx, const float *states_d, const float *action
   r.grad = grad_d;
   r.loss_part = W.loss_part;
   r.loss_splits = blocks;
-  r.inv_b = inv_b;
+  r.inv_b = coef.inv_b;
   r.logstd = ctx->params + NA.logstd_off;
   r.act_dim = A;
-  r.ent_coef = entropy_coef * ctx->ent_log_share;
+  r.ent_coef = logged_ent_coef(coef, ctx->ent_log_share);
   r.loss_out = loss_d;
   double slab_floats = 0;
   for (int i = 0; i < ns; ++i) slab_floats += static_cast<double>(r.seg[i].nsplit) * r.seg[i].len;

@@ -11,6 +11,7 @@
 
 #include "ctx.h"
 #include "fused_policy.h"
+#include "ppo_loss.h"
 
 namespace ppo {
 
@@ -68,8 +69,7 @@ int wide_observe(ppo_ctx *ctx, double *window_d, const double *obs_d, const uint
                  hipStream_t st);
 int wide_minibatch_grad(ppo_ctx *ctx, const float *states_d, const float *actions_d,
                         const float *old_logp_d, const float *adv_d, const float *vtarget_d,
-                        const int32_t *rows_d, int b, const int32_t *count_d, float clip_lo,
-                        float clip_hi, float entropy_coef, float inv_b, float inv_ba,
+                        const int32_t *rows_d, int b, const int32_t *count_d, const LossCoef &coef,
                         float *grad_d, float *loss_d, hipStream_t st);
 
 }  // namespace ppo
