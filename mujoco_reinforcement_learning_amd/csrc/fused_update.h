@@ -72,10 +72,10 @@ struct AdamPackArgs {
 };
 int adam_pack_launch(const AdamPackArgs &a, const TimRec &rec, hipStream_t st);
 
-// The single-rank optimizer-step tail of a staged minibatch, in one launch: blocks
-// [0, ceil(P/256)) fold the slabs (reduce_slab_block) and apply Adam + the weight-image refresh
-// to the parameters they just reduced (a.g is the reduced gradient, also written); the remaining
-// blocks gather the NEXT minibatch's rows from the staged records (b = 0: none).
+// The single-rank optimizer-step tail of a staged minibatch, in one launch: one block per 128
+// parameters folds the slabs (reduce_slabs.h's order) and applies Adam + the weight-image refresh
+// to the parameters it just reduced (a.g is the reduced gradient, also written); further blocks
+// gather the NEXT minibatch's rows from the staged records (b = 0: none).
 struct TailArgs {
   AdamPackArgs a;
   const int32_t *rows;
@@ -85,6 +85,14 @@ struct TailArgs {
   float *srow;
   int b;
   bool reduce;  // false: no slab reduction, Adam on the gradient already in a.g (data parallel)
+  // reduce: the fused launch's slab layout (slab k of parameter i at slabs[k * slab_stride + i],
+  // nsplit slabs).  With it, the parameter blocks wholly inside a net's W1 -- blocks
+  // [fast_lo[z], fast_hi[z]), marked by step_tail_launch after it has checked the W1 segments of
+  // the ReduceArgs against this layout -- take the tail's segment-free path.  slabs null: none.
+  const float *slabs;
+  int64_t slab_stride;
+  int nsplit;
+  int fast_lo[2], fast_hi[2];
 };
 int step_tail_launch(const ReduceArgs &r, const TailArgs &t, const TimRec &rec, hipStream_t st);
 

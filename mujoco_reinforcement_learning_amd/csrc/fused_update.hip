@@ -342,21 +342,88 @@ __device__ __forceinline__ void tail_block(const ReduceArgs &r, const TailArgs &
              *reinterpret_cast<const float4 *>(a.m + i), *reinterpret_cast<const float4 *>(a.v + i));
 }
 
-// Blocks of G float4 groups x kRedChunks chunks (the per-parameter order of every G is the
-// same, reduce_slabs.h).  G = 32 (512 threads, 128 parameters a block) by default.  At 69 VGPRs a
-// CU holds 3 such blocks, so the headline's 1,115 run in two rounds; smaller blocks that fit in
-// one were measured slower all the same (PPO_TAIL_GROUPS, round 5: 1.32 ms per iteration at
-// G = 32, 1.38 at 16, 1.67 at 8).
+// Interior parameter block j (TailArgs::fast_lo / fast_hi: wholly inside one net's W1, on the
+// fused launch's slab layout): no segment table, no search, one barrier.  Every thread sums its
+// chunk's slabs of one float4 group (slab_sum_aligned: the order of slab_item_sum's aligned path)
+// into the partials tile; thread e < 4 G then combines the 16 chunk partials of parameter e in
+// chunk order (chunk_combine's order per component), applies Adam to it with the p / m / v it
+// loaded BEFORE its slab loads (three registers, so the third memory round trip of the segment
+// path overlaps the first), and writes the weight images: the row-major image as one 16-B run per
+// 8 parameters assembled with lane shuffles, the transposed image element by element.
 template <int G>
-__global__ __launch_bounds__(G * kRedChunks) void step_tail_kernel(ReduceArgs r, TailArgs t, int red_blocks) {
+__device__ __forceinline__ void tail_fast(const ReduceArgs &r, const TailArgs &t, int j, char *lds) {
+  constexpr int NP = 4 * G;
+  static_assert(NP % 64 == 0, "the lead threads fill whole waves (lane shuffles)");
+  const AdamPackArgs &a = t.a;
+  const int tid = threadIdx.x, grp = tid % G, chunk = tid / G;
+  const bool lead = tid < NP;
+  const int n0 = t.fast_hi[0] - t.fast_lo[0], z = j >= n0 ? 1 : 0;
+  const int k0 = (t.nsplit * chunk) / kRedChunks, k1 = (t.nsplit * (chunk + 1)) / kRedChunks;
+  const int64_t i0 = static_cast<int64_t>(z == 0 ? t.fast_lo[0] + j : t.fast_lo[1] + (j - n0)) * NP;
+  const int64_t i = i0 + tid;
+  float p = 0.f, m = 0.f, v = 0.f;
+  if (lead) {
+    p = a.p[i];
+    m = a.m[i];
+    v = a.v[i];
+  }
+  float4 *part = reinterpret_cast<float4 *>(lds);  // [kRedChunks][G]
+  part[chunk * G + grp] = slab_sum_aligned(t.slabs + i0 + 4 * grp, t.slab_stride, k0, k1);
+  lds_sync();
+  if (!lead) return;
+  const float *pf = reinterpret_cast<const float *>(part);  // [kRedChunks][NP]
+  float g = pf[tid];
+#pragma unroll
+  for (int c = 1; c < kRedChunks; ++c) g += pf[c * NP + tid];
+  r.grad[i] = g;
+  const float ns = z == 0 ? (a.sched ? a.sched[0] : a.neg_a) : (a.sched ? a.sched[1] : a.neg_c);
+  const float bc2 = a.sched ? a.sched[2] : a.bc2;
+  p = adam_elem(p, g, m, v, ns, a.w1, a.b2, a.omb2, bc2, a.eps);
+  a.p[i] = p;
+  a.m[i] = m;
+  a.v[i] = v;
+  const int H = a.H;
+  const uint32_t e1 = static_cast<uint32_t>(i - a.off_w1[z]);
+  const int o = static_cast<int>(e1 / static_cast<uint32_t>(H));
+  const int c = static_cast<int>(e1 % static_cast<uint32_t>(H));
+  const uint32_t hb = bf16_bits(p);
+  reinterpret_cast<uint16_t *>(a.w1bt[z])[w_frag(c, o, H)] = static_cast<uint16_t>(hb);
+  // columns c..c+7 of row o (c % 8 == 0 on every 8th lane) are one 16-B fragment run
+  const uint32_t pair = hb | (static_cast<uint32_t>(__shfl_down(static_cast<int>(hb), 1)) << 16);
+  const uint32_t q1 = static_cast<uint32_t>(__shfl_down(static_cast<int>(pair), 2));
+  const uint32_t q2 = static_cast<uint32_t>(__shfl_down(static_cast<int>(pair), 4));
+  const uint32_t q3 = static_cast<uint32_t>(__shfl_down(static_cast<int>(pair), 6));
+  if ((tid & 7) == 0)
+    *reinterpret_cast<uint4 *>(a.w1b[z] + w_frag(o, c, H)) = make_uint4(pair, q1, q2, q3);
+}
+
+// Workgroups of G float4 groups x kRedChunks chunks (512 threads, 128 parameters a block at
+// G = 32; the per-parameter order does not depend on G, reduce_slabs.h).  Blocks
+// [0, slow_blocks): one parameter block each on the segment path (tail_block) -- every block when
+// nothing is marked interior (the non-reducing mode), else the blocks that hold tensor
+// boundaries, biases, heads, log-std and W0; then the next minibatch's record gather; then one
+// workgroup per interior block (tail_fast).  At 77 VGPRs a CU holds 3 workgroups, so the
+// headline's 1,115 run in two rounds; what was measured against that is in DESIGN.md s4.
+template <int G>
+__global__ __launch_bounds__(G * kRedChunks) void step_tail_kernel(ReduceArgs r, TailArgs t,
+                                                                    int slow_blocks, int gather_blocks) {
   __shared__ __attribute__((aligned(16))) char scratch[red_scratch_bytes<G>()];
   constexpr int NT = G * kRedChunks;
   const int tid = threadIdx.x;
-  if (static_cast<int>(blockIdx.x) >= red_blocks) {  // the next minibatch's record gather
-    tail_gather(t, (static_cast<int64_t>(blockIdx.x) - red_blocks) * NT + tid);
+  int bid = blockIdx.x;
+  if (bid < slow_blocks) {
+    // the bid-th parameter block outside the interior ranges (ascending, disjoint)
+    if (bid >= t.fast_lo[0]) bid += t.fast_hi[0] - t.fast_lo[0];
+    if (bid >= t.fast_lo[1]) bid += t.fast_hi[1] - t.fast_lo[1];
+    tail_block<G>(r, t, bid, red_scratch<G>(scratch));
     return;
   }
-  tail_block<G>(r, t, blockIdx.x, red_scratch<G>(scratch));
+  bid -= slow_blocks;
+  if (bid < gather_blocks) {  // the next minibatch's record gather
+    tail_gather(t, static_cast<int64_t>(bid) * NT + tid);
+    return;
+  }
+  tail_fast<G>(r, t, bid - gather_blocks, scratch);
 }
 
 // ============================================================================================
@@ -1156,28 +1223,48 @@ int adam_pack_launch(const AdamPackArgs &a, const TimRec &rec, hipStream_t st) {
   return 0;
 }
 
-// PPO_TAIL_GROUPS=8|16|32: float4 groups per step-tail block (A/B knob; bitwise the same sums)
-static const int g_tail_groups = [] {
-  const char *v = getenv("PPO_TAIL_GROUPS");
-  return v ? atoi(v) : 32;
-}();
+// Marks the parameter blocks (of `np` parameters) wholly inside net z's W1 as interior, when the
+// ReduceArgs' segment for that W1 is the fused launch's layout (t.slabs / slab_stride / nsplit),
+// so tail_fast reads exactly what the segment path would.
+static void mark_interior(const ReduceArgs &r, TailArgs &t, int np) {
+  for (int z = 0; z < 2; ++z) t.fast_lo[z] = t.fast_hi[z] = 0;
+  if (!t.reduce || !t.slabs || t.slab_stride % 4 != 0 || t.nsplit < 1 || t.a.H % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(t.slabs) % 16 != 0)
+    return;
+  int64_t prev_hi = 1;  // block 0 also folds the loss partials: always on the segment path
+  for (int z = 0; z < 2; ++z) {
+    const int64_t off = t.a.off_w1[z], len = static_cast<int64_t>(t.a.H) * t.a.H;
+    bool ok = false;
+    for (int s = 0; s < r.nseg; ++s) {
+      const ReduceSeg &g = r.seg[s];
+      ok = ok || (g.dst == off && g.len == len && g.src == t.slabs + off &&
+                  g.stride == t.slab_stride && g.nsplit == t.nsplit);
+    }
+    const int64_t lo = std::max<int64_t>(prev_hi, ceil_div(off, np)), hi = (off + len) / np;
+    if (!ok || off % 8 != 0 || lo >= hi) {
+      t.fast_lo[z] = t.fast_hi[z] = static_cast<int>(prev_hi);
+      continue;
+    }
+    t.fast_lo[z] = static_cast<int>(lo);
+    t.fast_hi[z] = static_cast<int>(hi);
+    prev_hi = hi;
+  }
+}
 
-int step_tail_launch(const ReduceArgs &r, const TailArgs &t, const TimRec &rec, hipStream_t st) {
-  PPO_REQUIRE(t.a.H % 4 == 0 && t.a.din >= 1 && t.a.din <= kFusedKX &&
-                  (!t.reduce || r.total == t.a.n),
-              "step tail: H=%d din=%d", t.a.H, t.a.din);
-  auto go = [&](auto gc) {
-    constexpr int G = decltype(gc)::value, NT = G * kRedChunks;
-    const int red_blocks = static_cast<int>(ceil_div(t.a.n, 4 * G));
-    const int gather_blocks = static_cast<int>(ceil_div(static_cast<int64_t>(t.b) * 8, NT));
-    TimRec named = rec;  // the launched instantiation's name (rocprof's, for the agreement check)
-    if (tim_active()) named.name = intern_name("step_tail_kernel<%d>", G);
-    launch_k(named, step_tail_kernel<G>, dim3(red_blocks + gather_blocks), dim3(NT), 0, st, r, t,
-             red_blocks);
-  };
-  if (g_tail_groups == 8) go(std::integral_constant<int, 8>{});
-  else if (g_tail_groups == 16) go(std::integral_constant<int, 16>{});
-  else go(std::integral_constant<int, 32>{});
+int step_tail_launch(const ReduceArgs &r, const TailArgs &t_in, const TimRec &rec, hipStream_t st) {
+  PPO_REQUIRE(t_in.a.H % 4 == 0 && t_in.a.din >= 1 && t_in.a.din <= kFusedKX &&
+                  (!t_in.reduce || r.total == t_in.a.n),
+              "step tail: H=%d din=%d", t_in.a.H, t_in.a.din);
+  constexpr int G = kRedGroups, NT = G * kRedChunks;
+  TailArgs t = t_in;
+  mark_interior(r, t, 4 * G);
+  const int n_fast = (t.fast_hi[0] - t.fast_lo[0]) + (t.fast_hi[1] - t.fast_lo[1]);
+  const int slow_blocks = static_cast<int>(ceil_div(t.a.n, 4 * G)) - n_fast;
+  const int gather_blocks = static_cast<int>(ceil_div(static_cast<int64_t>(t.b) * 8, NT));
+  TimRec named = rec;  // the launched instantiation's name (rocprof's, for the agreement check)
+  if (tim_active()) named.name = intern_name("step_tail_kernel<%d>", G);
+  launch_k(named, step_tail_kernel<G>, dim3(slow_blocks + gather_blocks + n_fast), dim3(NT), 0, st,
+           r, t, slow_blocks, gather_blocks);
   PPO_LAUNCHED();
   return 0;
 }

@@ -1409,6 +1409,9 @@ extern "C" int ppo_update_step_staged(ppo_ctx *ctx, const int32_t *rows_d, int b
   t.srow = ctx->fsrow;
   t.b = q.direct ? 0 : next_b;  // direct: the next fused launch reads its rows itself
   t.reduce = true;
+  t.slabs = ctx->fslabs;  // the layout fused_reduce_args describes segment by segment
+  t.slab_stride = ctx->total_params;
+  t.nsplit = q.G;
   if (int rc = fused_forward_backward(ctx, q, st)) {
     note_gathered(ctx, nullptr, 0);
     return rc;

@@ -79,6 +79,38 @@ __device__ __forceinline__ int seg_find(const ReduceSeg *sseg, int nseg, int64_t
   return s;
 }
 
+// Splits [k0, k1) of the 4 consecutive parameters at src (16-B aligned, stride % 4 == 0): two
+// interleaved partial sums (even / odd split) so 8 independent loads stay in flight per thread;
+// the association is fixed.  The aligned path of slab_item_sum and the step tail's interior
+// blocks (fused_update.hip) both sum through here.
+__device__ __forceinline__ float4 slab_sum_aligned(const float *src, int64_t stride, int k0,
+                                                   int k1) {
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 acc1 = make_float4(0.f, 0.f, 0.f, 0.f);
+  int k = k0;
+#pragma unroll 4
+  for (; k + 1 < k1; k += 2) {
+    const float4 v = *reinterpret_cast<const float4 *>(src + k * stride);
+    const float4 u = *reinterpret_cast<const float4 *>(src + (k + 1) * stride);
+    acc.x += v.x;
+    acc.y += v.y;
+    acc.z += v.z;
+    acc.w += v.w;
+    acc1.x += u.x;
+    acc1.y += u.y;
+    acc1.z += u.z;
+    acc1.w += u.w;
+  }
+  if (k < k1) {
+    const float4 v = *reinterpret_cast<const float4 *>(src + k * stride);
+    acc.x += v.x;
+    acc.y += v.y;
+    acc.z += v.z;
+    acc.w += v.w;
+  }
+  return make_float4(acc.x + acc1.x, acc.y + acc1.y, acc.z + acc1.z, acc.w + acc1.w);
+}
+
 // Chunk `chunk`'s share (splits [k0, k1)) of parameters i..i+3: the one summation order every
 // slab reduction uses.  The aligned path keeps two interleaved partial sums (even / odd split)
 // so 8 independent loads stay in flight per thread; the association is fixed, so the result is
@@ -93,30 +125,7 @@ __device__ __forceinline__ float4 slab_item_sum(const ReduceArgs &q, const Reduc
   const int k0 = (g.nsplit * chunk) / kRedChunks, k1 = (g.nsplit * (chunk + 1)) / kRedChunks;
   if (off >= 0 && off + 3 < g.len && g.stride % 4 == 0 &&
       reinterpret_cast<uintptr_t>(g.src) % 16 == 0) {
-    const float *src = g.src + off;
-    float4 acc1 = make_float4(0.f, 0.f, 0.f, 0.f);
-    int k = k0;
-#pragma unroll 4
-    for (; k + 1 < k1; k += 2) {
-      const float4 v = *reinterpret_cast<const float4 *>(src + k * g.stride);
-      const float4 u = *reinterpret_cast<const float4 *>(src + (k + 1) * g.stride);
-      acc.x += v.x;
-      acc.y += v.y;
-      acc.z += v.z;
-      acc.w += v.w;
-      acc1.x += u.x;
-      acc1.y += u.y;
-      acc1.z += u.z;
-      acc1.w += u.w;
-    }
-    if (k < k1) {
-      const float4 v = *reinterpret_cast<const float4 *>(src + k * g.stride);
-      acc.x += v.x;
-      acc.y += v.y;
-      acc.z += v.z;
-      acc.w += v.w;
-    }
-    acc = make_float4(acc.x + acc1.x, acc.y + acc1.y, acc.z + acc1.z, acc.w + acc1.w);
+    acc = slab_sum_aligned(g.src + off, g.stride, k0, k1);
   } else if (off >= 0) {
     float a4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
