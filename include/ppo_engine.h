@@ -116,6 +116,26 @@ int ppo_observe_act(ppo_ctx *ctx, double *window_d, const double *obs_d, const u
                     int all_reset, const int32_t *bounds, int n_bounds, int normalize,
                     float *state_d, int n, const float *eps_d, uint64_t seed, uint64_t offset,
                     float *action_d, float *logp_d, float *value_d, float *mean_d, void *stream);
+/* A whole T-step rollout of the synthetic device VecEnv (ppo_synthetic_env_step's dynamics) and
+ * the actor in ONE launch: per step what ppo_synthetic_env_step + ppo_observe_act (actor outputs)
+ * compute, bitwise, with each workgroup keeping its 32 envs for all t_len steps.  Streams as
+ * ppo_synthetic_env_step: base_obs (T+1, N, O) f32, base_reward / base_term (T, N).  window_d
+ * (N, O) f64 holds the reset observations on entry and observation T on exit.  noise_d (T, N, A)
+ * is the pre-drawn sampling noise (ppo_philox_normal_ctr); seed / offset are carried for symmetry
+ * with ppo_observe_act and not read.  Outputs, time-major: states (T+1, N, O), actions (T, N, A),
+ * logp (T, N), reward (T, N) f64, terminated (T, N) u8.  Values are not computed here: run
+ * ppo_value_batch over states afterwards.  Needs the fused bf16 path (ppo_ctx_fused_active),
+ * W = 1, O <= 32 and hidden width 256; anything else is an error. */
+int ppo_rollout_synthetic(ppo_ctx *ctx, const float *base_obs_d, const float *base_reward_d,
+                          const uint8_t *base_term_d, int t_len, int n, double *window_d,
+                          const int32_t *bounds, int n_bounds, int normalize, float *states_d,
+                          const float *noise_d, uint64_t seed, uint64_t offset, float *actions_d,
+                          float *logp_d, double *reward_d, uint8_t *terminated_d, void *stream);
+/* The critic's value of `rows` rows of standardised f32 states (rows, O) -> values_d (rows):
+ * per row bitwise the value ppo_observe_act / ppo_policy_step write on the fused bf16 path.
+ * Same requirements as ppo_rollout_synthetic. */
+int ppo_value_batch(ppo_ctx *ctx, const float *states_d, int64_t rows, float *values_d,
+                    void *stream);
 /* Refresh the bf16 weight images the fused kernels (or the wide bf16-resident layered path,
  * csrc/wide_path.h) read from the bound f32 parameters; call after the parameters change outside
  * ppo_minibatch_grad (Adam steps, loads) and before ppo_observe_act.  No-op unless a bf16 path

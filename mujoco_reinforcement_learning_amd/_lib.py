@@ -142,6 +142,11 @@ _SIGNATURES = {
     "ppo_observe_act": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                 c_int, c_void_p, c_int, c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ppo_rollout_synthetic": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                      c_void_p, POINTER(c_int32), c_int, c_int, c_void_p, c_void_p,
+                                      c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
+    "ppo_value_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "ppo_ctx_fused_active": (c_int, [c_void_p]),
     "ppo_host_register": (c_int, [c_void_p, c_int64]),
     "ppo_host_unregister": (c_int, [c_void_p]),

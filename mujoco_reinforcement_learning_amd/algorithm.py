@@ -158,10 +158,21 @@ class PPOEngine:
         self.environment_helper.t = t_len  # the host-side step counter the replay skipped
         return buf
 
+    def _persistent_ok(self) -> bool:
+        """The one-launch rollout (EngineConfig.persistent_rollout): exactly the device synthetic
+        VecEnv, f64 rewards, and the fused bf16 engine with its rollout entry point."""
+        helper, eng = self.environment_helper, self.agent.engine
+        return (bool(getattr(self.run.engine_config, "persistent_rollout", True)) and
+                getattr(helper, "device_rollout", False) is True and
+                hasattr(eng, "rollout_synthetic") and bool(getattr(eng, "fused", False)) and
+                self.buffer.reward.dtype == torch.float64 and self.buffer.window == 1)
+
     def _rollout_fused(self, base_off: int) -> RolloutBuffer:
         """Rollout through ppo_observe_act: per step one env launch (helper.step_raw) and one
         engine launch (window push + standardisation + actor/critic + sampling); same values as
-        the step / get_state / policy_step sequence below."""
+        the step / get_state / policy_step sequence below.  Where :meth:`_persistent_ok` holds,
+        the T steps are one launch and the values one more (ppo_rollout_synthetic,
+        ppo_value_batch), with the same values again."""
         helper, eng, buf = self.environment_helper, self.agent.engine, self.buffer
         n, t_len, a = buf.num_envs, buf.horizon, buf.act_dim
         helper.reset()
@@ -180,6 +191,20 @@ class PPOEngine:
                 self._noise = torch.empty(t_len, n, a, device=self.agent.device)
             noise = self._noise
             E.philox_normal(seed, base_off, noise, counter=getattr(eng, "_rng_counter", None))
+        if noise is not None and self._persistent_ok():
+            # the device VecEnv needs nothing from the host between steps: all T steps of env +
+            # actor in one launch, each workgroup keeping its envs, then the critic in one batched
+            # pass over the stored states (nothing inside the rollout reads a value) -- the same
+            # values as the per-step launches below, bit for bit
+            eng.rollout_synthetic(helper.base_obs, helper.base_reward, helper.base_terminated,
+                                  window, norm, buf.states, noise, buf.actions, buf.logp,
+                                  buf.reward, buf.terminated, seed=seed, offset=base_off)
+            eng.value_batch(buf.states, buf.values)
+            # the host-side bookkeeping the per-step path leaves behind
+            helper.t = t_len
+            helper.timestep.reward = buf.reward[t_len - 1]
+            helper.timestep.terminated = buf.terminated[t_len - 1]
+            return buf
         eps = noise[0] if noise is not None else self._eps(n, a)[0]
         eng.observe_act(window, buf.states[0], normalize=norm, eps=eps, seed=seed,
                         offset=base_off, action=buf.actions[0], logp=buf.logp[0],

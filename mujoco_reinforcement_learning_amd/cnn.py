@@ -358,6 +358,7 @@ class SyntheticPixelVecEnvHelper:
 
     writes_into_buffer = True
     graph_safe = True
+    device_rollout = False     # frames, not the state env's dynamics
 
     def __init__(self, streams: Optional[dict] = None, run: Optional[Run] = None,
                  device: Optional[torch.device] = None, seed: int = 0, p_terminate: float = 0.0):

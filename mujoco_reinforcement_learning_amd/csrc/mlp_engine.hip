@@ -1517,6 +1517,106 @@ extern "C" int ppo_observe_act(ppo_ctx *ctx, double *window_d, const double *obs
   return policy_fused_launch(q, rec, as_stream(stream));
 }
 
+// the shapes the persistent rollout kernels are compiled for
+static int rollout_ctx_ok(const ppo_ctx *ctx, const char *who) {
+  PPO_REQUIRE(fused_active(ctx), "%s: needs the fused bf16 path (ppo_ctx_fused_active)", who);
+  PPO_REQUIRE(ctx->cfg.window == 1 && ctx->cfg.obs_dim <= kFusedKX && ctx->fused_hidden == 256,
+              "%s: needs W = 1, O <= %d and hidden width 256 (W = %d, O = %d, H = %d)", who,
+              kFusedKX, ctx->cfg.window, ctx->cfg.obs_dim, ctx->fused_hidden);
+  return 0;
+}
+
+extern "C" int ppo_rollout_synthetic(ppo_ctx *ctx, const float *base_obs_d,
+                                     const float *base_reward_d, const uint8_t *base_term_d,
+                                     int t_len, int n, double *window_d, const int32_t *bounds,
+                                     int n_bounds, int normalize, float *states_d,
+                                     const float *noise_d, uint64_t seed, uint64_t offset,
+                                     float *actions_d, float *logp_d, double *reward_d,
+                                     uint8_t *terminated_d, void *stream) {
+  (void)seed;    // carried for symmetry with ppo_observe_act: the kernel reads the pre-drawn noise
+  (void)offset;
+  if (int rc = check_ctx(ctx)) return rc;
+  if (int rc = rollout_ctx_ok(ctx, "ppo_rollout_synthetic")) return rc;
+  PPO_REQUIRE(base_obs_d && base_reward_d && base_term_d && window_d && states_d && noise_d &&
+                  actions_d && logp_d && reward_d && terminated_d,
+              "ppo_rollout_synthetic: null buffer");
+  PPO_REQUIRE(n > 0 && t_len > 0, "ppo_rollout_synthetic: bad shape n=%d t=%d", n, t_len);
+  PPO_REQUIRE(n <= ctx->cfg.max_rows, "ppo_rollout_synthetic: n=%d exceeds max_rows=%d", n,
+              ctx->cfg.max_rows);
+  PPO_REQUIRE(n_bounds >= 0 && n_bounds < 16, "ppo_rollout_synthetic: too many slices (%d)",
+              n_bounds);
+  const int o = ctx->cfg.obs_dim;
+  PolicySlices tab{};
+  tab.count = normalize ? n_bounds : 0;
+  for (int i = 0; i <= n_bounds && normalize; ++i) {
+    PPO_REQUIRE(bounds != nullptr, "ppo_rollout_synthetic: null bounds");
+    PPO_REQUIRE(bounds[i] >= 0 && bounds[i] <= o && (i == 0 || bounds[i] >= bounds[i - 1]),
+                "ppo_rollout_synthetic: bounds must be ascending within [0, O]");
+    tab.edge[i] = bounds[i];
+  }
+  TimingScope timing_scope(ctx);
+  FusedNet nets[2];
+  fused_nets(ctx, nets);
+  RolloutArgs q{};
+  q.net = nets[0];
+  q.logstd = ctx->params + ctx->net[0].logstd_off;
+  q.n = n;
+  q.obs_dim = o;
+  q.act_dim = ctx->cfg.act_dim;
+  q.act = ctx->cfg.activation;
+  q.hidden = ctx->fused_hidden;
+  q.t_len = t_len;
+  q.omv = ctx->cfg.output_max_value;
+  q.window_d = window_d;
+  q.base_obs = base_obs_d;
+  q.base_reward = base_reward_d;
+  q.base_term = base_term_d;
+  q.tab = tab;
+  q.normalize = normalize;
+  q.noise = noise_d;
+  q.states = states_d;
+  q.actions = actions_d;
+  q.logp = logp_d;
+  q.reward = reward_d;
+  q.terminated = terminated_d;
+  q.stamps = (ctx->fstamp_on && q.act == PPO_ACT_RELU) ? ctx->fstamps : nullptr;
+  if (q.stamps) ctx->fstamp_g = 128;
+  const double H = ctx->fused_hidden, A = q.act_dim, rows = static_cast<double>(n) * t_len;
+  const TimRec rec{KC_POLICY_HEAD,
+                   tim_active() ? intern_name("rollout_persistent_kernel<%d, %d>", ctx->fused_hidden, q.act)
+                                : nullptr,
+                   2.0 * rows * (o * H + H * H + A * H),
+                   rows * (8.0 * o + 8.0 * A + 4.0 + 4.0 + 1.0 + 8.0 + 1.0) + 12.0 * n * o};
+  return rollout_persistent_launch(q, rec, as_stream(stream));
+}
+
+extern "C" int ppo_value_batch(ppo_ctx *ctx, const float *states_d, int64_t rows, float *values_d,
+                               void *stream) {
+  if (int rc = check_ctx(ctx)) return rc;
+  if (int rc = rollout_ctx_ok(ctx, "ppo_value_batch")) return rc;
+  PPO_REQUIRE(states_d && values_d, "ppo_value_batch: null buffer");
+  PPO_REQUIRE(rows > 0, "ppo_value_batch: rows=%lld must be positive", static_cast<long long>(rows));
+  int num_cu = 0;
+  PPO_HIP_TRY(hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  TimingScope timing_scope(ctx);
+  FusedNet nets[2];
+  fused_nets(ctx, nets);
+  ValueBatchArgs q{};
+  q.net = nets[1];
+  q.obs_dim = ctx->cfg.obs_dim;
+  q.act = ctx->cfg.activation;
+  q.hidden = ctx->fused_hidden;
+  q.rows = rows;
+  q.states = states_d;
+  q.values = values_d;
+  const double H = ctx->fused_hidden, o = q.obs_dim;
+  const TimRec rec{KC_POLICY_HEAD,
+                   tim_active() ? intern_name("value_batch_kernel<%d, %d>", ctx->fused_hidden, q.act)
+                                : nullptr,
+                   2.0 * rows * (o * H + H * H + H), rows * (4.0 * o + 4.0)};
+  return value_batch_launch(q, num_cu, rec, as_stream(stream));
+}
+
 extern "C" int ppo_minibatch_grad(ppo_ctx *ctx, const float *states_d, const float *actions_d,
                                   const float *old_logp_d, const float *adv_d,
                                   const float *vtarget_d, const int32_t *rows_d, int b,

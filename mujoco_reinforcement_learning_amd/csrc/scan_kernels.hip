@@ -12,6 +12,7 @@
 
 #include "adam_elem.h"
 #include "common.h"
+#include "device_env.h"
 #include "gae_pipe.h"
 #include "row_stats.h"
 #include "timing.h"
@@ -366,16 +367,10 @@ __global__ void synthetic_env_step_kernel(const float *__restrict__ base_obs,
   if (i >= static_cast<uint32_t>(n) * static_cast<uint32_t>(o)) return;
   const uint32_t env = i / static_cast<uint32_t>(o);
   const uint32_t f = i - env * static_cast<uint32_t>(o);
-  const double act = static_cast<double>(action[env * a + (f % static_cast<uint32_t>(a))]);
-  obs_out[i] = static_cast<double>(base_obs[i]) + 0.1 * act;
+  obs_out[i] = denv::next_obs(base_obs[i], action[env * a + (f % static_cast<uint32_t>(a))]);
   if (f == 0) {
-    double ctrl = 0.0;
-    for (int j = 0; j < a; ++j) {
-      const double aj = static_cast<double>(action[env * a + j]);
-      ctrl = ctrl + aj * aj;
-    }
-    reward_out[env] = static_cast<double>(base_reward[env]) - 0.01 * ctrl;
-    term_out[env] = base_term[env];
+    reward_out[env] = denv::reward(base_reward[env], a, [&](int j) { return action[env * a + j]; });
+    term_out[env] = denv::terminated(base_term[env]);
   }
 }
 
@@ -402,19 +397,15 @@ __global__ __launch_bounds__(256) void synthetic_test_step_kernel(
       const double x0 = static_cast<double>(base_obs[f]);
       for (int s = 0; s < w; ++s) row[s] = x0;
     } else {
-      const double x = static_cast<double>(nxt[f]) + 0.1 * static_cast<double>(action[f % a]);
+      const double x = denv::next_obs(nxt[f], action[f % a]);
       for (int s = 0; s + 1 < w; ++s) row[s] = row[s + 1];
       row[w - 1] = x;
     }
   }
   __syncthreads();  // every thread has read *step
   if (threadIdx.x == 0) {
-    double ctrl = 0.0;
-    for (int j = 0; j < a; ++j) {
-      const double aj = static_cast<double>(action[j]);
-      ctrl = ctrl + aj * aj;
-    }
-    const double r = static_cast<double>(base_reward[static_cast<int64_t>(kt) * n_envs]) - 0.01 * ctrl;
+    const double r = denv::reward(base_reward[static_cast<int64_t>(kt) * n_envs], a,
+                                  [&](int j) { return action[j]; });
     *reward_sum = *reward_sum + r;
     *term_out = term ? 1 : 0;
     *step = term ? 0 : k + 1;

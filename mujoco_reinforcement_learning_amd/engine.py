@@ -208,6 +208,59 @@ class Engine:
             ptr(obs_next), n, o, w, self.act_dim, t, ptr(eps), seed, base_offset,
             _stream(self.device)))
 
+    def rollout_synthetic(self, base_obs, base_reward, base_terminated, window: torch.Tensor,
+                          normalize: bool, states, noise, actions, logp, reward, terminated,
+                          seed: int = 0, offset: int = 0) -> None:
+        """All T steps of the synthetic device VecEnv and the actor in one launch
+        (ppo_rollout_synthetic): per step what ``synthetic_env_step`` + :meth:`observe_act`
+        compute, without the values (:meth:`value_batch` over ``states`` afterwards).  ``window``
+        (N, O, 1) f64 holds the reset observations on entry and observation T on exit; ``noise``
+        (T, N, A) is the pre-drawn sampling noise; the outputs are the rollout buffer's
+        time-major arrays."""
+        n, o, w = window.shape
+        t = actions.shape[0]
+        _need(window, "window", torch.float64, device=self.device)
+        if (o, w) != (self.obs_dim, self.window) or w != 1:
+            raise RuntimeError(f"window is {(o, w)}, expected (O, 1) = {(self.obs_dim, 1)}")
+        _need(base_obs, "base_obs", torch.float32, device=self.device)
+        _need(base_reward, "base_reward", torch.float32, device=self.device)
+        _need(base_terminated, "base_terminated", None, device=self.device)
+        if (base_obs.shape[0] < t + 1 or tuple(base_obs.shape[1:]) != (n, o)
+                or base_reward.shape[0] < t or tuple(base_reward.shape[1:]) != (n,)
+                or base_terminated.shape[0] < t or tuple(base_terminated.shape[1:]) != (n,)
+                or base_terminated.element_size() != 1):
+            raise RuntimeError("streams must be base_obs (>=T+1, N, O), base_reward / "
+                               "base_terminated (>=T, N)")
+        _need(states, "states", torch.float32, device=self.device)
+        if states.numel() != (t + 1) * n * o:
+            raise RuntimeError("states must hold (T+1, N, O) floats")
+        _need(noise, "noise", torch.float32, (t, n, self.act_dim), self.device)
+        _need(actions, "actions", torch.float32, (t, n, self.act_dim), self.device)
+        _need(logp, "logp", torch.float32, (t, n), self.device)
+        _need(reward, "reward", torch.float64, (t, n), self.device)
+        _need(terminated, "terminated", None, (t, n), self.device)
+        if terminated.element_size() != 1:
+            raise RuntimeError("terminated must be a 1-byte dtype")
+        edges = slice_edges(o)
+        arr = (ctypes.c_int32 * len(edges))(*edges)
+        check(self.lib.ppo_rollout_synthetic(
+            self._ctx, ptr(base_obs), ptr(base_reward), ptr(base_terminated), t, n, ptr(window),
+            arr, len(edges) - 1, int(normalize), ptr(states), ptr(noise), seed, offset,
+            ptr(actions), ptr(logp), ptr(reward), ptr(terminated), _stream(self.device)))
+
+    def value_batch(self, states: torch.Tensor, values: torch.Tensor) -> None:
+        """The critic's values of ``states`` (..., O) f32 into ``values`` (...) in one launch
+        (ppo_value_batch): per row bitwise what :meth:`observe_act` / :meth:`policy_step` write
+        on the fused bf16 path."""
+        _need(states, "states", torch.float32, device=self.device)
+        _need(values, "values", torch.float32, device=self.device)
+        rows = values.numel()
+        if rows == 0 or states.numel() != rows * self.in_dim:
+            raise RuntimeError(f"states must hold {self.in_dim} floats for each of the "
+                               f"{rows} values")
+        check(self.lib.ppo_value_batch(self._ctx, ptr(states), rows, ptr(values),
+                                       _stream(self.device)))
+
     def set_precision(self, precision: str) -> None:
         """GEMM precision: "f32" (parity with the reference, default) or "bf16" (bf16 operands,
         f32 accumulation; activations, params and optimizer state stay f32)."""

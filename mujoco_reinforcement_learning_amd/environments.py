@@ -54,6 +54,8 @@ class SyntheticVecEnvHelper:
 
     writes_into_buffer = True  # step(reward_out=, terminated_out=) / get_state(out=)
     graph_safe = True          # every step is device work on fixed buffers (hipGraph-capturable)
+    device_rollout = True      # the dynamics need only the streams and the actions, so a whole
+    #                            rollout can run as one launch (Engine.rollout_synthetic)
 
     def __init__(self, streams: Optional[dict] = None, run: Optional[Run] = None,
                  device: Optional[torch.device] = None, seed: int = 0, p_terminate: float = 0.0):
@@ -193,6 +195,7 @@ class HostPhysicsVecEnvHelper(SyntheticVecEnvHelper):
     for all envs every step."""
 
     graph_safe = False
+    device_rollout = False     # the physics runs on host cores
 
     def __init__(self, streams: Optional[dict] = None, run: Optional[Run] = None,
                  device: Optional[torch.device] = None, seed: int = 0, p_terminate: float = 0.0,

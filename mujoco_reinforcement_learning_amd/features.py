@@ -140,6 +140,10 @@ class EngineConfig:
     precision: "f32" (every GEMM in f32, parity with the reference) or "bf16" (fc-layer GEMM
          operands rounded to bf16 with f32 accumulation; params, optimizer state, activations,
          heads, losses and GAE stay f32) -- BASELINE.json configs[1].
+    persistent_rollout: on the fused bf16 path with rng="philox" and the device synthetic VecEnv
+         (``device_rollout``), run all T steps of env + actor in one launch
+         (ppo_rollout_synthetic) and the critic in one batched pass over the stored states
+         (ppo_value_batch), instead of two launches per step.  Same values, bit for bit.
     """
     rng: str = "torch"
     critic_hidden_shapes: Optional[List[int]] = None
@@ -148,6 +152,7 @@ class EngineConfig:
     rollout_graph: bool = True
     train_graph: bool = True
     precision: str = "f32"
+    persistent_rollout: bool = True
 
 
 REFERENCE_CRITIC_HIDDEN = (128, 128)  # models/critic.py:14

@@ -21,6 +21,7 @@ def make_run(num_envs: int = 4096, horizon: int = 128, obs_dim: int = 17, act_di
              advantage_scaler: float = 1.0, use_bias: bool = True, output_max_value: float = 1.0,
              rng: str = "torch", seed: int = 0, dp_mode: str = "local",
              rollout_graph: bool = True, train_graph: bool = True, precision: str = "f32",
+             persistent_rollout: bool = True,
              experiment_path: str = "/tmp/ppo_engine_run",
              feature_extractor: str = "MLP", latent: int = 256, extractor_layers: int = 1,
              replace: bool = True) -> Run:
@@ -68,4 +69,5 @@ def make_run(num_envs: int = 4096, horizon: int = 128, obs_dim: int = 17, act_di
                                           seed=seed,
                                           dp_mode=dp_mode, rollout_graph=rollout_graph,
                                           train_graph=train_graph,
-                                          precision=precision))
+                                          precision=precision,
+                                          persistent_rollout=persistent_rollout))
