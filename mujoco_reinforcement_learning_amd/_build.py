@@ -11,7 +11,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SOURCES = ["csrc/scan_kernels.hip", "csrc/mlp_engine.hip", "csrc/fused_update.hip",
+SOURCES = ["csrc/scan_kernels.hip", "csrc/mlp_engine.hip", "csrc/layered_engine.hip",
+           "csrc/timing.hip", "csrc/reduce_slabs.hip", "csrc/fused_update.hip",
            "csrc/fused_policy.hip", "csrc/bilstm.hip", "csrc/host_rollout.hip",
            "csrc/cnn_engine.hip", "csrc/gemm_ops_fwd_nk.hip", "csrc/gemm_ops_fwd_kn.hip",
            "csrc/gemm_ops_dx.hip", "csrc/gemm_ops_wgrad.hip", "csrc/wide_gemm.hip",

@@ -36,7 +36,7 @@ from . import _lib
 from ._lib import check, ptr
 from .agent import _ACT_NAMES, ExponentialLRFacade, FlatAdam, PPOEngineAgent
 from .buffer import RolloutBuffer
-from .engine import _need, _stream
+from .engine import RngCounterEngine, _need, _stream
 from .environments import Timestep, make_synthetic_streams
 from .features import Run
 from .models import _Block, move_to_flat
@@ -87,8 +87,13 @@ class EngineCNNCritic(nn.Module):
         return self._agent.get_state_value(x)
 
 
-class CNNEngine:
+class CNNEngine(RngCounterEngine):
     """One ``ppo_cnn_ctx``: encoder + MLP shapes, workspace and split-K slabs."""
+
+    _abi = {"destroy": "ppo_cnn_ctx_destroy", "bind": "ppo_cnn_bind_params",
+            "entropy_share": "ppo_cnn_loss_entropy_share", "precision": "ppo_cnn_set_precision",
+            "rng_counter": "ppo_cnn_set_rng_counter", "timing": "ppo_cnn_timing",
+            "timing_kernel": "ppo_cnn_timing_kernel"}
 
     fused = False  # the staged-record path of the MLP engine does not apply
 
@@ -129,38 +134,8 @@ class CNNEngine:
         self.precision = "f32"
         self._params = None
 
-    def __del__(self):
-        ctx = getattr(self, "_ctx", None)
-        if ctx is not None and ctx.value:
-            try:
-                self.lib.ppo_cnn_ctx_destroy(ctx)
-            except Exception:  # interpreter shutdown
-                pass
-            self._ctx = None
-
     def param_offsets(self) -> list:
         return list(self._offsets)
-
-    def bind(self, flat_params: torch.Tensor) -> None:
-        _need(flat_params, "flat_params", torch.float32, (self.n_params,), self.device)
-        check(self.lib.ppo_cnn_bind_params(self._ctx, ptr(flat_params)))
-        self._params = flat_params
-
-    def loss_entropy_share(self, share: float) -> None:
-        """Share of the entropy bonus in the LOGGED actor loss (ppo_cnn_loss_entropy_share)."""
-        check(self.lib.ppo_cnn_loss_entropy_share(self._ctx, float(share)))
-
-    def set_precision(self, precision: str) -> None:
-        if precision not in _lib.PREC_CODES:
-            raise ValueError(f"unknown precision {precision!r}; use one of {sorted(_lib.PREC_CODES)}")
-        check(self.lib.ppo_cnn_set_precision(self._ctx, _lib.PREC_CODES[precision]))
-        self.precision = precision
-
-    def set_rng_counter(self, counter: Optional[torch.Tensor]) -> None:
-        if counter is not None:
-            _need(counter, "counter", torch.int64, (1,), self.device)
-        check(self.lib.ppo_cnn_set_rng_counter(self._ctx, ptr(counter)))
-        self._rng_counter = counter
 
     def pack_weights(self) -> None:
         """The conv weights are repacked inside every forward (ppo_cnn_*)."""
@@ -218,36 +193,6 @@ class CNNEngine:
             self._ctx, ptr(states), ptr(actions), ptr(old_logp), ptr(adv), ptr(vtarget),
             ptr(rows), int(b), ptr(grad), ptr(loss), clip_lo, clip_hi, entropy_coef, inv_b,
             inv_ba, _stream(self.device)))
-
-    # ---- measurement (the Engine.timing* contract of bench.py) ----------------------------------
-    def timing(self, enable: bool, capacity: int = 65536) -> None:
-        check(self.lib.ppo_cnn_timing(self._ctx, int(enable), int(capacity)))
-
-    def timing_kernels(self) -> dict:
-        out = {}
-        n_k = self.lib.ppo_cnn_timing_kernel(self._ctx, -1, None, None, None, None, None, None)
-        check(min(n_k, 0))
-        for i in range(n_k):
-            name, cls = ctypes.c_char_p(), ctypes.c_int()
-            ms, fl, by = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
-            cnt = ctypes.c_int64()
-            check(self.lib.ppo_cnn_timing_kernel(self._ctx, i, ctypes.byref(name),
-                                                 ctypes.byref(cls), ctypes.byref(ms),
-                                                 ctypes.byref(cnt), ctypes.byref(fl),
-                                                 ctypes.byref(by)))
-            out[name.value.decode()] = {
-                "class": self.lib.ppo_kernel_class_name(cls.value).decode(), "ms": ms.value,
-                "launches": cnt.value, "flops": fl.value, "bytes": by.value}
-        return out
-
-    def timing_read(self) -> dict:
-        out = {}
-        for name, k in self.timing_kernels().items():
-            c = out.setdefault(k["class"], {"ms": 0.0, "launches": 0, "flops": 0.0, "bytes": 0.0})
-            for key in ("ms", "launches", "flops", "bytes"):
-                c[key] += k[key]
-        return out
-
 
 class PixelRolloutBuffer(RolloutBuffer):
     """RolloutBuffer (time-major, buffer.py) whose states are u8 frames (T+1, N, H*W*C);

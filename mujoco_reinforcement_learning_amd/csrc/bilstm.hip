@@ -55,8 +55,6 @@ constexpr int kSplits = 32;           // split-K slabs of the weight gradients (
 constexpr int64_t kAlign = 16;        // floats: every flat tensor starts 64-B aligned
 constexpr int64_t kWsAlign = 64;
 
-static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-
 struct LstmLayer {
   int in;
   int64_t w_ih[2], w_hh[2], b_ih[2], b_hh[2];  // flat offsets, direction d
@@ -676,10 +674,6 @@ __global__ __launch_bounds__(256) void lstm_params_bf16_kernel(const float *__re
   }
 }
 
-__global__ __launch_bounds__(kRedThreads) void lstm_reduce_kernel(ReduceArgs q) {
-  (void)reduce_slab_block(q, blockIdx.x);
-}
-
 // xg16 (bf16 mode): the rows as bf16 instead of f32 (GEMM operands only), one (row, step) of O
 // values per ld16-wide row; rows == nullptr: the states in order (the rollout's windows)
 __global__ void lstm_gather_rows_kernel(const float *__restrict__ states,
@@ -957,11 +951,6 @@ bool feat16_on(const ppo_lstm_ctx *x) {
   return x->prec == PPO_PREC_BF16 && x->cfg.activation == PPO_ACT_RELU &&
          (x->cfg.window * 2 * x->cfg.latent) % 4 == 0 && !(v && atoi(v) == 0);
 }
-
-struct TimingScope {
-  explicit TimingScope(ppo_lstm_ctx *x) { g_tim = x->tim.on ? &x->tim : nullptr; }
-  ~TimingScope() { g_tim = nullptr; }
-};
 
 void add_mlp(Mlp &m, int in, const ppo_lstm_cfg &c, int out, int final_act, int64_t &off,
              std::vector<int64_t> &offs) {
@@ -1818,7 +1807,7 @@ extern "C" int ppo_lstm_forward(ppo_lstm_ctx *x, const float *state_d, int n, fl
   if (int rc = check_rows(x, n)) return rc;
   if (n == 0) return 0;
   PPO_HIP_TRY(hipSetDevice(x->device));
-  TimingScope ts(x);
+  TimingScope ts(x->tim);
   hipStream_t st = as_stream(stream);
   if (int rc = forward_rollout(x, state_d, n, st)) return rc;
   const int A = x->cfg.act_dim, W = x->cfg.window;
@@ -1855,7 +1844,7 @@ extern "C" int ppo_lstm_policy_step(ppo_lstm_ctx *x, const float *state_d, int n
   if (int rc = check_rows(x, n)) return rc;
   if (n == 0) return 0;
   PPO_HIP_TRY(hipSetDevice(x->device));
-  TimingScope ts(x);
+  TimingScope ts(x->tim);
   hipStream_t st = as_stream(stream);
   if (int rc = forward_rollout(x, state_d, n, st)) return rc;
   const int nl = x->cfg.n_hidden;
@@ -1889,7 +1878,7 @@ extern "C" int ppo_lstm_minibatch_grad(ppo_lstm_ctx *x, const float *states_d,
   PPO_REQUIRE(b > 0, "ppo_lstm_minibatch_grad: empty minibatch");
   PPO_HIP_TRY(hipSetDevice(x->device));
   const LossCoef coef{clip_lo, clip_hi, entropy_coef, inv_b, inv_ba};
-  TimingScope ts(x);
+  TimingScope ts(x->tim);
   hipStream_t st = as_stream(stream);
   const ppo_lstm_cfg &c = x->cfg;
   const int W = c.window, A = c.act_dim, H = c.latent, nl = c.n_hidden;
@@ -1945,17 +1934,11 @@ extern "C" int ppo_lstm_minibatch_grad(ppo_lstm_ctx *x, const float *states_d,
   }
   // slabs -> flat gradient, tensor by tensor in a fixed split order
   ReduceArgs r{};
-  int ns = 0;
   for (size_t i = 0; i < x->offsets.size(); ++i) {
-    PPO_REQUIRE(ns < kMaxSegs, "ppo_lstm_minibatch_grad: too many tensors (%zu)", x->offsets.size());
-    ReduceSeg &g = r.seg[ns++];
-    g.dst = x->offsets[i];
-    g.len = (i + 1 < x->offsets.size() ? x->offsets[i + 1] : x->total) - x->offsets[i];
-    g.src = x->slabs + x->offsets[i];
-    g.stride = x->total;
-    g.nsplit = x->splits;
+    const int64_t len = (i + 1 < x->offsets.size() ? x->offsets[i + 1] : x->total) - x->offsets[i];
+    if (int rc = add_seg(r, x->offsets[i], len, x->slabs + x->offsets[i], x->total, x->splits))
+      return rc;
   }
-  r.nseg = ns;
   r.total = x->total;
   r.grad = grad_d;
   bool aligned = x->total % 4 == 0 && reinterpret_cast<uintptr_t>(x->slabs) % 16 == 0 &&
@@ -1970,9 +1953,9 @@ extern "C" int ppo_lstm_minibatch_grad(ppo_lstm_ctx *x, const float *states_d,
       launch_k(rec, lstm_reduce_fast_kernel<16>, grid, dim3(256), 0, st, grad_d, x->slabs, x->total);
     else
       launch_k(rec, lstm_reduce_fast_kernel<32>, grid, dim3(256), 0, st, grad_d, x->slabs, x->total);
-  } else
-    launch_k(TimRec{KC_REDUCE, "reduce_slabs_kernel", 0.0, 0.0}, lstm_reduce_kernel,
-             dim3(ceil_div(x->total, kRedParams)), dim3(kRedThreads), 0, st, r);
+  } else {
+    return reduce_slabs_launch(r, TimRec{KC_REDUCE, "reduce_slabs_kernel", 0.0, 0.0}, st);
+  }
   PPO_LAUNCHED();
   return 0;
 }

@@ -17,7 +17,7 @@
 //   MLP backward (split-K slabs; the input gradient of layer 0 times relu'(features) is the
 //     encoder's output gradient, CHW)
 //   conv L3 WGRAD + DGRAD, L2 WGRAD + DGRAD, L1 WGRAD (per-split slabs)
-//   reduce_slabs_kernel: every slab -> the flat gradient in a fixed order (deterministic)
+//   reduce_slabs_kernel (reduce_slabs.hip): every slab -> the flat gradient in a fixed order
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -43,8 +43,6 @@ constexpr int kConvMaxSplits = 256;   // split-K slabs of a conv weight gradient
 constexpr int kHeadSplits = 256;      // row blocks of the update head (log-std / loss partials)
 constexpr int64_t kAlign = 16;        // floats: every flat tensor starts 64-B aligned
 constexpr int64_t kWsAlign = 64;
-
-static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
 struct MlpLayer {
   int in, out, act;
@@ -165,10 +163,6 @@ __global__ __launch_bounds__(256) void cnn_update_head_kernel(HeadArgs q) {
   }
 }
 
-__global__ __launch_bounds__(kRedThreads) void cnn_reduce_kernel(ReduceArgs q) {
-  (void)reduce_slab_block(q, blockIdx.x);
-}
-
 // ---- synthetic pixel VecEnv (bench / test harness) ----------------------------------------------
 __device__ __forceinline__ uint32_t mix32(uint32_t seed, uint32_t t, uint32_t n, uint32_t i) {
   uint32_t h = (i * 0x9E3779B1u) ^ (t * 0x85EBCA77u + n * 0xC2B2AE3Du + seed * 0x27D4EB2Fu);
@@ -275,11 +269,6 @@ struct ppo_cnn_ctx {
 };
 
 namespace {
-
-struct TimingScope {
-  explicit TimingScope(ppo_cnn_ctx *x) { g_tim = x->tim.on ? &x->tim : nullptr; }
-  ~TimingScope() { g_tim = nullptr; }
-};
 
 void add_mlp(Mlp &m, int in, const ppo_cnn_cfg &c, int out, int final_act, bool bias, int64_t &off,
              std::vector<int64_t> &offs) {
@@ -984,7 +973,7 @@ extern "C" int ppo_cnn_forward(ppo_cnn_ctx *x, const uint8_t *frames_d, int n, f
   if (n == 0) return 0;
   PPO_HIP_TRY(hipSetDevice(x->device));
   hipStream_t st = as_stream(stream);
-  TimingScope ts(x);
+  TimingScope ts(x->tim);
   if (int rc = forward_all(x, frames_d, nullptr, n, st)) return rc;
   const int64_t fb = sizeof(float) * static_cast<int64_t>(n) * kFeatures;
   if (feat_actor_d) PPO_HIP_TRY(hipMemcpyAsync(feat_actor_d, x->feat[0], fb, hipMemcpyDeviceToDevice, st));
@@ -1015,7 +1004,7 @@ extern "C" int ppo_cnn_policy_step(ppo_cnn_ctx *x, const uint8_t *frames_d, int 
   if (n == 0) return 0;
   PPO_HIP_TRY(hipSetDevice(x->device));
   hipStream_t st = as_stream(stream);
-  TimingScope ts(x);
+  TimingScope ts(x->tim);
   if (int rc = forward_all(x, frames_d, nullptr, n, st)) return rc;
   HeadArgs h{};
   h.ya = x->act[0][x->mlp[0].n - 1];
@@ -1051,7 +1040,7 @@ extern "C" int ppo_cnn_minibatch_grad(ppo_cnn_ctx *x, const uint8_t *frames_d,
   PPO_HIP_TRY(hipSetDevice(x->device));
   const LossCoef coef{clip_lo, clip_hi, entropy_coef, inv_b, inv_ba};
   hipStream_t st = as_stream(stream);
-  TimingScope ts(x);
+  TimingScope ts(x->tim);
   const int A = x->cfg.act_dim;
   if (int rc = forward_all(x, frames_d, rows_d, b, st)) return rc;
   const int head_splits = std::min(kHeadSplits, std::max(1, b / 64));
@@ -1082,47 +1071,31 @@ extern "C" int ppo_cnn_minibatch_grad(ppo_cnn_ctx *x, const uint8_t *frames_d,
 
   // slabs -> flat gradient in ascending tensor order, each in a fixed split order
   ReduceArgs r{};
-  int ns = 0;
   auto seg = [&](int64_t dst, int64_t len, const float *src, int64_t stride, int nsplit) {
-    ReduceSeg &g = r.seg[ns++];
-    g.dst = dst;
-    g.len = len;
-    g.src = src;
-    g.stride = stride;
-    g.nsplit = nsplit;
+    return add_seg(r, dst, len, src, stride, nsplit);
   };
   const int64_t ksz[3] = {static_cast<int64_t>(L1::cout) * L1::kdim,
                           static_cast<int64_t>(L2::cout) * L2::kdim,
                           static_cast<int64_t>(L3::cout) * L3::kdim};
   const int cout[3] = {L1::cout, L2::cout, L3::cout};
+  int rc = 0;
   for (int z = 0; z < 2; ++z) {
-    if (z == 0) seg(x->logstd_off, A, x->ls_part, A, head_splits);
+    if (z == 0) rc |= seg(x->logstd_off, A, x->ls_part, A, head_splits);
     for (int l = 0; l < 3; ++l) {
       const int ns_l = x->cslab_splits_last[l];
-      seg(x->conv[z][l].w, ksz[l], x->cslab[z][l], x->cslab_stride[l], ns_l);
-      seg(x->conv[z][l].b, cout[l], x->cslab[z][l] + ksz[l], x->cslab_stride[l], ns_l);
+      rc |= seg(x->conv[z][l].w, ksz[l], x->cslab[z][l], x->cslab_stride[l], ns_l);
+      rc |= seg(x->conv[z][l].b, cout[l], x->cslab[z][l] + ksz[l], x->cslab_stride[l], ns_l);
     }
     for (int l = 0; l < x->mlp[z].n; ++l) {
       const MlpLayer &L = x->mlp[z].l[l];
-      seg(L.w, static_cast<int64_t>(L.out) * L.in, x->mlp_slabs + L.w, x->total, mlp_splits);
-      if (L.b >= 0) seg(L.b, L.out, x->mlp_slabs + L.b, x->total, mlp_splits);
+      rc |= seg(L.w, static_cast<int64_t>(L.out) * L.in, x->mlp_slabs + L.w, x->total, mlp_splits);
+      if (L.b >= 0) rc |= seg(L.b, L.out, x->mlp_slabs + L.b, x->total, mlp_splits);
     }
   }
-  PPO_REQUIRE(ns <= kMaxSegs, "ppo_cnn_minibatch_grad: %d tensors exceed the reduction table", ns);
-  r.nseg = ns;
-  r.total = x->total;
-  r.grad = grad_d;
-  r.loss_part = x->loss_part;
-  r.loss_splits = head_splits;
-  r.inv_b = coef.inv_b;
-  r.logstd = x->params + x->logstd_off;
-  r.act_dim = A;
-  r.ent_coef = logged_ent_coef(coef, x->ent_log_share);
-  r.loss_out = loss_d;
-  launch_k(TimRec{KC_REDUCE, "reduce_slabs_kernel", 0.0, 0.0}, cnn_reduce_kernel,
-           dim3(ceil_div(x->total, kRedParams)), dim3(kRedThreads), 0, st, r);
-  PPO_LAUNCHED();
-  return 0;
+  if (rc) return rc;  // add_seg: 0 or PPO_EINVAL
+  set_loss_tail(r, x->total, grad_d, x->loss_part, head_splits, coef, x->params + x->logstd_off, A,
+                x->ent_log_share, loss_d);
+  return reduce_slabs_launch(r, TimRec{KC_REDUCE, "reduce_slabs_kernel", 0.0, 0.0}, st);
 }
 
 extern "C" int ppo_cnn_timing(ppo_cnn_ctx *x, int enable, int capacity) {

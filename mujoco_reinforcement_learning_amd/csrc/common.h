@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
 
 #include "ppo_engine.h"
 
@@ -37,6 +38,13 @@ void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int ceil_div(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) / b); }
+inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+// An integer experiment knob from the environment (callers read it once, into a static).
+inline int env_knob(const char *name, int dflt) {
+  const char *v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
 
 // ---- activations (network_block_creator.py:54-55: config["activation"]()) -------------------
 // Forward matches torch's CPU kernels; backward is expressed on the layer OUTPUT y, which is what

@@ -1,5 +1,6 @@
 // The MLP actor-critic context (ppo_ctx, include/ppo_engine.h) and its layer descriptors, shared by
-// the layered / fused engine (mlp_engine.hip) and the wide bf16-resident path (wide_engine.hip).
+// its C-ABI and fused-path glue (mlp_engine.hip), the layered path (layered_engine.hip) and the wide
+// bf16-resident path (wide_engine.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -36,7 +37,7 @@ struct ppo_ctx {
   ppo::NetDesc net[2];
   int64_t total_params;
   float *params;
-  float *slabs;          // (kSlabSplits, total_params)
+  float *slabs;          // (kSlabSplits, total_params); the k*Splits extents: layered_path.h
   float *head_part;      // logstd partials (kHeadSplits, A) + loss partials (kHeadSplits, 2)
   float *head_w_part;    // fused head dW/db partials (kHeadSplits, hw_stride), UpdateHeadArgs
   const uint64_t *rng_counter;  // device Philox offset base (nullable), read at kernel run time

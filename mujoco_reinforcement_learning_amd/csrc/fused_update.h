@@ -1,5 +1,5 @@
 // Persistent fused minibatch update (precision mode bf16, two equal hidden layers): host-side
-// argument block and launchers, shared by mlp_engine.hip (ppo_minibatch_grad) and
+// argument block and launchers, shared by mlp_engine.hip (the staged and ppo_minibatch_grad entry points) and
 // fused_update.hip (the kernels).
 #pragma once
 

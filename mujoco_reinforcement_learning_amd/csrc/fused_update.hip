@@ -21,7 +21,8 @@
 // Weight gradients are summed over all chunks of the workgroup in registers (dW1: 8 32x32
 // tiles per wave; dW0: one tile per wave), so HBM sees only the bf16 minibatch inputs, the
 // L2-resident bf16 weights and, once per workgroup, one partial-gradient slab in the flat
-// parameter layout.  reduce_slabs_kernel then folds the G slabs in a fixed order.
+// parameter layout.  reduce_slabs_kernel (reduce_slabs.hip) or the step tail then folds the G slabs
+// in a fixed order.
 //
 // Numerics = oracle.use_bf16_hidden_gemms: every hidden-layer product takes bf16(RNE) operands
 // with f32 accumulation; the heads (forward, dH, head dW) and every bias gradient are f32 on the

@@ -1,4 +1,4 @@
-// The f32 / bf16 MFMA GEMM templates of the layered engine (mlp_engine.hip) and their host-side
+// The f32 / bf16 MFMA GEMM templates of the layered path (layered_engine.hip) and their host-side
 // launch helpers, shared with the BiLSTM feature extractor (bilstm.hip).
 //
 //   FWD      C = act(A B^T + bias)            A [rows][k] (A_MK), B [n][k] (B_NK) or [k][n] (B_KN)
@@ -785,12 +785,8 @@ static int launch_gemm(const GemmBatch &gb, int nprob, int max_m, int max_n, hip
   return 0;
 }
 
-// Experiment knobs for the large-M tiles (read once): PPO_GEMM_NBUF=1|2 LDS buffers,
+// Experiment knobs for the large-M tiles (env_knob, read once): PPO_GEMM_NBUF=1|2 LDS buffers,
 // PPO_GEMM_WIDE=1 for 128x256 tiles (4 waves, 64x128 per wave).
-static int env_knob(const char *name, int dflt) {
-  const char *v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
 static const int g_nbuf = env_knob("PPO_GEMM_NBUF", 2);
 static const int g_wide = env_knob("PPO_GEMM_WIDE", 0);
 // The 128x128 tiles as 8 waves of 64x32 (two waves per SIMD; PPO_GEMM_W8=0: 4 waves of 64x64) --
@@ -834,6 +830,5 @@ static int run_rowwise(const GemmBatch &gb, int nprob, int rows, int max_n, hipS
   if (max_n <= 32) return launch_gemm<1, 1, 4, 1, A_KM, B_KN, EPI_PARTIAL>(gb, nprob, max_m, max_n, st);
   return launch_big<2, 2, 2, 2, A_KM, B_KN, EPI_PARTIAL>(gb, nprob, max_m, max_n, st);
 }
-
 
 }  // namespace ppo

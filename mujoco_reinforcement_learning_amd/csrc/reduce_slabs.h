@@ -1,6 +1,8 @@
 // Deterministic split-K reduction of per-workgroup partial-gradient slabs into the flat
 // gradient, plus the minibatch loss scalars (ppo.py:121,133 `loss.item()` values).  Shared by
-// reduce_slabs_kernel (mlp_engine.hip) and step_tail_kernel (fused_update.hip).
+// reduce_slabs_kernel (reduce_slabs.hip: the fold every engine launches through
+// reduce_slabs_launch), step_tail_kernel (fused_update.hip) and wide_reduce_kernel
+// (wide_engine.hip); every engine builds its segment table with add_seg / set_loss_tail.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +10,8 @@
 #include <cstdint>
 
 #include "common.h"
+#include "ppo_loss.h"
+#include "timing.h"
 
 namespace ppo {
 
@@ -31,6 +35,34 @@ struct ReduceArgs {
   float ent_coef;
   float *loss_out;
 };
+
+// Appends one segment to the table.  Segments go in ascending dst order; their order is the
+// fold order.
+inline int add_seg(ReduceArgs &r, int64_t dst, int64_t len, const float *src, int64_t stride,
+                   int nsplit) {
+  PPO_REQUIRE(r.nseg < kMaxSegs, "slab reduction: more than %d gradient segments", kMaxSegs);
+  r.seg[r.nseg++] = ReduceSeg{dst, len, src, stride, nsplit};
+  return 0;
+}
+
+// The fields after the segment table: the flat gradient (total floats) and the loss scalars.
+inline void set_loss_tail(ReduceArgs &r, int64_t total, float *grad, const float *loss_part,
+                          int loss_splits, const LossCoef &coef, const float *logstd, int act_dim,
+                          float ent_log_share, float *loss_out) {
+  r.total = total;
+  r.grad = grad;
+  r.loss_part = loss_part;
+  r.loss_splits = loss_splits;
+  r.inv_b = coef.inv_b;
+  r.logstd = logstd;
+  r.act_dim = act_dim;
+  r.ent_coef = logged_ent_coef(coef, ent_log_share);
+  r.loss_out = loss_out;
+}
+
+// reduce_slabs_kernel over the whole table: ceil(total / kRedParams) blocks of kRedThreads
+// (reduce_slabs.hip).
+int reduce_slabs_launch(const ReduceArgs &r, const TimRec &rec, hipStream_t st);
 
 // Block = kRedGroups float4 groups x kRedChunks split-chunks (512 threads): each thread sums
 // 1/kRedChunks of the splits for 4 consecutive parameters (tensors start 16-float aligned, so a

@@ -66,13 +66,19 @@ const char *intern_name(const char *fmt, ...);
 
 inline bool tim_active() { return g_tim != nullptr; }
 
-// Shared bodies of the per-context timing entry points (ppo_ctx_timing / ppo_cnn_timing, ...):
+// Shared bodies of the per-context timing entry points (ppo_ctx_timing / ppo_cnn_timing, ...),
+// implemented in timing.hip with the rest of this header's state:
 // enable (re)allocates `capacity` event pairs and clears the totals; read folds pending records.
 int timing_enable(Timing &t, int enable, int capacity);
 int timing_read_class(Timing &t, int kclass, double *total_ms, int64_t *launches, double *flops,
                       double *bytes);
 int timing_read_kernel(Timing &t, int index, const char **name, int *kclass, double *total_ms,
                        int64_t *launches, double *flops, double *bytes);
+
+struct TimingScope {  // routes this thread's launches to a ctx's timing while it is enabled
+  explicit TimingScope(Timing &t) { g_tim = t.on ? &t : nullptr; }
+  ~TimingScope() { g_tim = nullptr; }
+};
 
 struct FreeTimingScope {
   FreeTimingScope() { g_tim = (g_free_tim && g_free_tim->on) ? g_free_tim : nullptr; }

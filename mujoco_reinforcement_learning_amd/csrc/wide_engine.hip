@@ -12,7 +12,7 @@
 //   WGRAD    slab[s] = dz^T h_{L-1}, then per hidden layer dZ_l^T h_{l-1} (split-K over rows)
 //   DGRAD    dZ_{l-1} = (dZ_l W_l) * relu'(h_{l-1}), written over h_{l-1}, + bias column sums
 //   reduce   fixed-order sums of the slabs / partials into the flat gradient + loss scalars
-// The same formulas as update_head_kernel / policy_head_kernel (mlp_engine.hip) on the bf16
+// The same formulas as update_head_kernel / policy_head_kernel (layered_engine.hip) on the bf16
 // emulation's operands: every product's operands rounded to bf16, f32 accumulation, biases,
 // losses and activation derivatives in f32 (the derivative of ReLU from the bf16 output: the
 // sign of a value survives RNE rounding, so it is the f32 output's).
@@ -35,7 +35,6 @@ namespace ppo {
 using wide::WideBatch;
 using wide::WideProblem;
 
-static inline int64_t rup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 constexpr int kWideSplits = 16;      // WGRAD split-K slabs of the hidden layers (at most)
 // Split-K slabs of the hidden-layer WGRAD: PPO_WIDE_SPLITS (1 .. 16, default 8).  Every slab is
 // a full f32 copy of the layer's gradient written by WGRAD and read by wide_reduce_kernel, so at
@@ -77,17 +76,17 @@ int wide_alloc(ppo_ctx *ctx) {
   if (ctx->wide || !wide_shapes_ok(ctx)) return 0;
   WideWork *w = new (std::nothrow) WideWork();
   PPO_REQUIRE(w != nullptr, "wide_alloc: out of host memory");
-  const int64_t R = rup(ctx->cfg.max_rows, 256);
+  const int64_t R = align_up(ctx->cfg.max_rows, 256);
   w->rpad = static_cast<int>(R);
   const int din = ctx->cfg.obs_dim * ctx->cfg.window;
-  w->ldx = static_cast<int>(rup(din, 128));  // whole 8-k-step groups for the fused rollout
+  w->ldx = static_cast<int>(align_up(din, 128));  // whole 8-k-step groups for the fused rollout
   const int blocks = static_cast<int>(R / kWideLossRows);
   // carve-out in bytes; every buffer 256-B aligned, 1 KB of slack after each (tile reads past a
   // row end stay inside the allocation)
   int64_t bytes = 0;
   auto take = [&](int64_t b) {
     const int64_t o = bytes;
-    bytes += rup(b, 256) + 1024;
+    bytes += align_up(b, 256) + 1024;
     return o;
   };
   struct Off {
@@ -101,7 +100,7 @@ int wide_alloc(ppo_ctx *ctx) {
     const NetDesc &nd = ctx->net[z];
     WideNetWork &wn = w->net[z];
     for (int l = 0; l < nd.n_hidden; ++l) {
-      wn.ldh[l] = static_cast<int>(rup(nd.layer[l].out, 64));
+      wn.ldh[l] = static_cast<int>(align_up(nd.layer[l].out, 64));
       off[z].h[l] = take(R * wn.ldh[l] * 2);
       off[z].dh[l] = take(R * wn.ldh[l] * 2);
       off[z].cs[l] = take((R / 64) * nd.layer[l].out * 4);
@@ -115,10 +114,10 @@ int wide_alloc(ppo_ctx *ctx) {
     WideNetWork &wn = w->net[z];
     for (int l = 0; l <= nd.n_hidden; ++l) {
       const LayerDesc &L = nd.layer[l];
-      wn.ldw[l] = static_cast<int>(rup(L.in, 64));
-      wn.ldwt[l] = static_cast<int>(rup(L.out, 64));
-      const int64_t a = rup(rup(L.out, 128) * wn.ldw[l] * 2, 256);
-      const int64_t b = rup(rup(L.in, 128) * wn.ldwt[l] * 2, 256);
+      wn.ldw[l] = static_cast<int>(align_up(L.in, 64));
+      wn.ldwt[l] = static_cast<int>(align_up(L.out, 64));
+      const int64_t a = align_up(align_up(L.out, 128) * wn.ldw[l] * 2, 256);
+      const int64_t b = align_up(align_up(L.in, 128) * wn.ldwt[l] * 2, 256);
       off[z].w[l] = bytes;
       bytes += a;
       off[z].wt[l] = bytes;
@@ -142,8 +141,8 @@ int wide_alloc(ppo_ctx *ctx) {
       WideNetWork &wn = w->net[z];
       for (int l = 0; l <= nd.n_hidden; ++l) {
         const LayerDesc &L = nd.layer[l];
-        wn.wf_tiles[l] = static_cast<int>(rup(L.out, 32) / 32);
-        wn.wf_ks[l] = static_cast<int>(rup(L.in, 128) / 16);
+        wn.wf_tiles[l] = static_cast<int>(align_up(L.out, 32) / 32);
+        wn.wf_ks[l] = static_cast<int>(align_up(L.in, 128) / 16);
         off_wf[z][l] = take(static_cast<int64_t>(wn.wf_tiles[l]) * wn.wf_ks[l] * 512 * 2);
       }
     }
@@ -455,7 +454,7 @@ int wide_pack(ppo_ctx *ctx, hipStream_t st, bool frag, const GatherArgs *gather)
         d.in = L.in;
         d.transposed = t;
         d.dst = t ? wn.wt[l] : wn.w[l];
-        d.rows = static_cast<int>(t ? rup(L.in, 128) : rup(L.out, 128));
+        d.rows = static_cast<int>(t ? align_up(L.in, 128) : align_up(L.out, 128));
         d.cols = t ? wn.ldwt[l] : wn.ldw[l];
         d.blocks = blocks;
         blocks += (d.rows / kPackT) * (d.cols / kPackT);
@@ -477,7 +476,6 @@ int wide_pack(ppo_ctx *ctx, hipStream_t st, bool frag, const GatherArgs *gather)
   PPO_LAUNCHED();
   return 0;
 }
-
 
 // ============================================================================================
 // Forward through the hidden layers and the head pre-activations (both nets per launch)
@@ -736,7 +734,7 @@ int wide_observe(ppo_ctx *ctx, double *window_d, const double *obs_d, const uint
   q.reset = reset_d;
   q.all_reset = all_reset;
   q.n = n;
-  q.rows_pad = static_cast<int>(rup(n, 64));
+  q.rows_pad = static_cast<int>(align_up(n, 64));
   q.o = o;
   q.w = w;
   q.tab = tab;
@@ -1122,7 +1120,7 @@ int wide_policy_step(ppo_ctx *ctx, const float *state_d, int n, const float *eps
   WideWork &W = *ctx->wide;
   const bool use[2] = {action_d || logp_d || mean_d, value_d != nullptr};
   if (!use[0] && !use[1]) return 0;
-  const int rows_pad = static_cast<int>(rup(n, 64));
+  const int rows_pad = static_cast<int>(align_up(n, 64));
   if (pack)
     if (int rc = wide_pack(ctx, st)) return rc;
   if (!staged)  // (wide_observe wrote x already)
@@ -1407,7 +1405,7 @@ int wide_minibatch_grad(ppo_ctx *ctx, const float *states_d, const float *action
                         const int32_t *rows_d, int b, const int32_t *count_d, const LossCoef &coef,
                         float *grad_d, float *loss_d, hipStream_t st) {
   WideWork &W = *ctx->wide;
-  const int rows_pad = static_cast<int>(rup(b, 64));
+  const int rows_pad = static_cast<int>(align_up(b, 64));
   const int64_t P = ctx->total_params;
   const int A = ctx->cfg.act_dim;
   NetDesc &NA = ctx->net[0], &NC = ctx->net[1];
@@ -1535,53 +1533,26 @@ int wide_minibatch_grad(ppo_ctx *ctx, const float *states_d, const float *action
 
   // ---- fixed-order reduction into the flat gradient + loss scalars ----------------------------
   ReduceArgs r{};
-  int ns = 0;
   for (int z = 0; z < 2; ++z) {
     const NetDesc &nd = ctx->net[z];
-    if (z == 0) {
-      ReduceSeg &g = r.seg[ns++];
-      g.dst = nd.logstd_off;
-      g.len = A;
-      g.src = W.part;
-      g.stride = kWidePart;
-      g.nsplit = blocks;
-    }
+    if (z == 0)
+      if (int rc = add_seg(r, nd.logstd_off, A, W.part, kWidePart, blocks)) return rc;
     for (int l = 0; l <= nd.n_hidden; ++l) {
       const LayerDesc &L = nd.layer[l];
-      ReduceSeg &g = r.seg[ns++];
-      g.dst = L.w_off;
-      g.len = static_cast<int64_t>(L.out) * L.in;
-      g.src = ctx->slabs + L.w_off;
-      g.stride = P;
-      g.nsplit = splits_of[z][l];
-      if (L.b_off >= 0) {
-        ReduceSeg &gb = r.seg[ns++];
-        gb.dst = L.b_off;
-        gb.len = L.out;
-        if (l < nd.n_hidden) {
-          gb.src = W.net[z].colsum[l];
-          gb.stride = L.out;
-          gb.nsplit = colsum_rows[z][l];
-        } else {
-          gb.src = W.part + (z == 0 ? 32 : 64);
-          gb.stride = kWidePart;
-          gb.nsplit = blocks;
-        }
-      }
+      if (int rc = add_seg(r, L.w_off, static_cast<int64_t>(L.out) * L.in, ctx->slabs + L.w_off, P,
+                           splits_of[z][l]))
+        return rc;
+      if (L.b_off < 0) continue;
+      if (int rc = l < nd.n_hidden
+                       ? add_seg(r, L.b_off, L.out, W.net[z].colsum[l], L.out, colsum_rows[z][l])
+                       : add_seg(r, L.b_off, L.out, W.part + (z == 0 ? 32 : 64), kWidePart, blocks))
+        return rc;
     }
   }
-  r.nseg = ns;
-  r.total = P;
-  r.grad = grad_d;
-  r.loss_part = W.loss_part;
-  r.loss_splits = blocks;
-  r.inv_b = coef.inv_b;
-  r.logstd = ctx->params + NA.logstd_off;
-  r.act_dim = A;
-  r.ent_coef = logged_ent_coef(coef, ctx->ent_log_share);
-  r.loss_out = loss_d;
+  set_loss_tail(r, P, grad_d, W.loss_part, blocks, coef, ctx->params + NA.logstd_off, A,
+                ctx->ent_log_share, loss_d);
   double slab_floats = 0;
-  for (int i = 0; i < ns; ++i) slab_floats += static_cast<double>(r.seg[i].nsplit) * r.seg[i].len;
+  for (int i = 0; i < r.nseg; ++i) slab_floats += static_cast<double>(r.seg[i].nsplit) * r.seg[i].len;
   // the fold plan: fast groups (16-split aligned segments) by the fast blocks, the rest in runs
   WideRedPlan pl{};
   pl.fast_blocks = static_cast<int>(ceil_div(P, 4 * kRedThreads));
@@ -1597,7 +1568,7 @@ int wide_minibatch_grad(ppo_ctx *ctx, const float *states_d, const float *action
     ++pl.nslow;
     return 0;
   };
-  for (int i = 0; i < ns; ++i) {
+  for (int i = 0; i < r.nseg; ++i) {
     const ReduceSeg &g = r.seg[i];
     const bool fast = fast_seg(g);
     if (!fast) {

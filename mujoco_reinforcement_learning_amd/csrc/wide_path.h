@@ -2,7 +2,8 @@
 // backward with bf16-resident activations (PPO_PREC_BF16, ReLU nets the fused kernels do not
 // cover, e.g. Humanoid 3x512 with O=376 and A=17).  Kernels: wide_gemm.h (products),
 // wide_engine.hip (gather, heads, loss, weight images).  Entry points route here from
-// ppo_policy_step / ppo_minibatch_grad / ppo_pack_weights (mlp_engine.hip) when wide_active().
+// ppo_policy_step / ppo_minibatch_grad / ppo_pack_weights / ppo_observe_act (mlp_engine.hip) when
+// wide_active(); the f32 and remaining bf16 shapes take layered_path.h instead.
 #pragma once
 
 #include <hip/hip_runtime.h>

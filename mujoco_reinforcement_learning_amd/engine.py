@@ -43,8 +43,98 @@ def slice_edges(obs_dim: int) -> list:
     return edges
 
 
-class Engine:
+class EngineBase:
+    """What the three context front ends (``Engine``, ``CNNEngine``, ``LSTMEngine``) share: the
+    handle's lifetime, parameter binding, precision, the logged entropy share and the per-launch
+    timing.  ``_abi`` names each engine's C-ABI functions; a subclass sets ``lib``, ``_ctx``,
+    ``device`` and ``n_params`` in its ``__init__``."""
+
+    _abi: dict = {}  # destroy, bind, entropy_share, precision, timing, timing_kernel[, rng_counter]
+
+    def _call(self, key: str, *args):
+        return getattr(self.lib, self._abi[key])(self._ctx, *args)
+
+    def __del__(self):
+        ctx = getattr(self, "_ctx", None)
+        if ctx is not None and ctx.value:
+            try:
+                self._call("destroy")
+            except Exception:  # interpreter shutdown
+                pass
+            self._ctx = None
+
+    def bind(self, flat_params: torch.Tensor) -> None:
+        _need(flat_params, "flat_params", torch.float32, (self.n_params,), self.device)
+        check(self._call("bind", ptr(flat_params)))
+        self._params = flat_params
+
+    def loss_entropy_share(self, share: float) -> None:
+        """Share of the entropy bonus in the LOGGED actor loss (ppo_*_loss_entropy_share)."""
+        check(self._call("entropy_share", float(share)))
+
+    def set_precision(self, precision: str) -> None:
+        """GEMM precision: "f32" (parity with the reference, default) or "bf16" (bf16 operands,
+        f32 accumulation; activations, params and optimizer state stay f32)."""
+        if precision not in _lib.PREC_CODES:
+            raise ValueError(f"unknown precision {precision!r}; use one of {sorted(_lib.PREC_CODES)}")
+        check(self._call("precision", _lib.PREC_CODES[precision]))
+        self.precision = precision
+
+    # ---- measurement (the timing* contract of bench.py) -----------------------------------
+    def timing(self, enable: bool, capacity: int = 65536) -> None:
+        """Record a HIP event pair around every kernel this context launches (live roofline)."""
+        check(self._call("timing", int(enable), int(capacity)))
+
+    def timing_kernels(self) -> dict:
+        """The timing records per kernel instantiation, keyed by the rocprofv3 kernel name:
+        {name: {"class": ..., "ms", "launches", "flops", "bytes"}}."""
+        out = {}
+        n_k = self._call("timing_kernel", -1, None, None, None, None, None, None)
+        check(min(n_k, 0))
+        for i in range(n_k):
+            name, cls = ctypes.c_char_p(), ctypes.c_int()
+            ms, fl, by = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+            cnt = ctypes.c_int64()
+            check(self._call("timing_kernel", i, ctypes.byref(name), ctypes.byref(cls),
+                             ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(fl),
+                             ctypes.byref(by)))
+            out[name.value.decode()] = {
+                "class": self.lib.ppo_kernel_class_name(cls.value).decode(), "ms": ms.value,
+                "launches": cnt.value, "flops": fl.value, "bytes": by.value}
+        return out
+
+    def timing_read(self) -> dict:
+        """{class: {"ms": total kernel ms, "launches": n, "flops": algorithmic, "bytes": ...}},
+        summed from :meth:`timing_kernels` (the classes that ran)."""
+        out = {}
+        for name, k in self.timing_kernels().items():
+            c = out.setdefault(k["class"], {"ms": 0.0, "launches": 0, "flops": 0.0, "bytes": 0.0})
+            for key in ("ms", "launches", "flops", "bytes"):
+                c[key] += k[key]
+        return out
+
+
+class RngCounterEngine(EngineBase):
+    """An engine whose sampling kernels can read a device-side Philox offset base.  A class of
+    its own because ``PPOEngine`` asks ``hasattr(engine, "set_rng_counter")`` before it captures
+    the rollout into a graph, and ``LSTMEngine`` has no such counter."""
+
+    def set_rng_counter(self, counter: Optional[torch.Tensor]) -> None:
+        """Philox offset base read on the device at kernel run time (int64 scalar tensor on this
+        device, or None): lets a graph-captured rollout replay with fresh noise."""
+        if counter is not None:
+            _need(counter, "counter", torch.int64, (1,), self.device)
+        check(self._call("rng_counter", ptr(counter)))
+        self._rng_counter = counter  # keep the buffer alive while the ctx may read it
+
+
+class Engine(RngCounterEngine):
     """One ``ppo_ctx``: network shapes + activation workspace + split-K slabs on one GPU."""
+
+    _abi = {"destroy": "ppo_ctx_destroy", "bind": "ppo_bind_params",
+            "entropy_share": "ppo_ctx_loss_entropy_share", "precision": "ppo_ctx_set_precision",
+            "rng_counter": "ppo_ctx_set_rng_counter", "timing": "ppo_ctx_timing",
+            "timing_kernel": "ppo_ctx_timing_kernel"}
 
     def __init__(self, obs_dim: int, window: int, act_dim: int, actor_hidden: Sequence[int],
                  critic_hidden: Sequence[int], activation: str = "relu",
@@ -83,15 +173,6 @@ class Engine:
         self._params = None
         self.precision = "f32"
 
-    def __del__(self):
-        ctx = getattr(self, "_ctx", None)
-        if ctx is not None and ctx.value:
-            try:
-                self.lib.ppo_ctx_destroy(ctx)
-            except Exception:  # interpreter shutdown
-                pass
-            self._ctx = None
-
     # ---- parameters ----------------------------------------------------------------------
     def param_offsets(self) -> list:
         """Flat offset of every parameter tensor (torch parameters() order, actor then critic)."""
@@ -99,11 +180,6 @@ class Engine:
         arr = (ctypes.c_int64 * n)()
         self.lib.ppo_param_offsets(self._ctx, arr, n)
         return list(arr)
-
-    def bind(self, flat_params: torch.Tensor) -> None:
-        _need(flat_params, "flat_params", torch.float32, (self.n_params,), self.device)
-        check(self.lib.ppo_bind_params(self._ctx, ptr(flat_params)))
-        self._params = flat_params
 
     # ---- A2-A4 ---------------------------------------------------------------------------
     def policy_step(self, state: torch.Tensor, eps: Optional[torch.Tensor] = None, seed: int = 0,
@@ -136,10 +212,6 @@ class Engine:
         _need(flat_grad, "flat_grad", torch.float32, (self.n_params,), self.device)
         check(self.lib.ppo_allreduce_grads(self._ctx, ptr(flat_grad), flat_grad.numel(),
                                            _stream(self.device)))
-
-    def loss_entropy_share(self, share: float) -> None:
-        """Share of the entropy bonus in the LOGGED actor loss (ppo_ctx_loss_entropy_share)."""
-        check(self.lib.ppo_ctx_loss_entropy_share(self._ctx, float(share)))
 
     def pack_weights(self) -> None:
         """Refresh the bf16 weight images of the fused kernels from the bound parameters (after
@@ -261,22 +333,6 @@ class Engine:
         check(self.lib.ppo_value_batch(self._ctx, ptr(states), rows, ptr(values),
                                        _stream(self.device)))
 
-    def set_precision(self, precision: str) -> None:
-        """GEMM precision: "f32" (parity with the reference, default) or "bf16" (bf16 operands,
-        f32 accumulation; activations, params and optimizer state stay f32)."""
-        if precision not in _lib.PREC_CODES:
-            raise ValueError(f"unknown precision {precision!r}; use one of {sorted(_lib.PREC_CODES)}")
-        check(self.lib.ppo_ctx_set_precision(self._ctx, _lib.PREC_CODES[precision]))
-        self.precision = precision
-
-    def set_rng_counter(self, counter: Optional[torch.Tensor]) -> None:
-        """Philox offset base read on the device at kernel run time (int64 scalar tensor on this
-        device, or None): lets a graph-captured rollout replay with fresh noise."""
-        if counter is not None:
-            _need(counter, "counter", torch.int64, (1,), self.device)
-        check(self.lib.ppo_ctx_set_rng_counter(self._ctx, ptr(counter)))
-        self._rng_counter = counter  # keep the buffer alive while the ctx may read it
-
     def fused_direct(self, enable: Optional[bool] = None) -> bool:
         """ppo_ctx_fused_direct: the 8-wave fused kernel reads the staged records through the row
         indices itself (True, default) or the gathered copy (False); returns the current mode."""
@@ -285,12 +341,9 @@ class Engine:
         return bool(self.lib.ppo_ctx_fused_direct(self._ctx, -1))
 
     # ---- measurement ---------------------------------------------------------------------
-    def timing(self, enable: bool, capacity: int = 65536) -> None:
-        """Record a HIP event pair around every kernel this context launches (live roofline)."""
-        check(self.lib.ppo_ctx_timing(self._ctx, int(enable), int(capacity)))
-
     def timing_read(self) -> dict:
-        """{class: {"ms": total kernel ms, "launches": n, "flops": algorithmic, "bytes": ...}}"""
+        """{class: {"ms": total kernel ms, "launches": n, "flops": algorithmic, "bytes": ...}},
+        read per class (ppo_ctx_timing_read): every class, the ones that did not run included."""
         out = {}
         n_cls = self.lib.ppo_ctx_timing_read(self._ctx, -1, None, None, None, None)
         for c in range(n_cls):
@@ -314,25 +367,6 @@ class Engine:
         n = self.lib.ppo_ctx_phase_stamps(self._ctx, 0, ctypes.c_void_p(out.data_ptr()), out.numel())
         check(min(n, 0))
         return out[:n].view(2, -1, 13)
-
-    def timing_kernels(self) -> dict:
-        """Same records per kernel instantiation, keyed by the rocprofv3 kernel name:
-        {name: {"class": ..., "ms", "launches", "flops", "bytes"}}."""
-        out = {}
-        n_k = self.lib.ppo_ctx_timing_kernel(self._ctx, -1, None, None, None, None, None, None)
-        check(min(n_k, 0))
-        for i in range(n_k):
-            name, cls = ctypes.c_char_p(), ctypes.c_int()
-            ms, fl, by = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
-            cnt = ctypes.c_int64()
-            check(self.lib.ppo_ctx_timing_kernel(self._ctx, i, ctypes.byref(name),
-                                                 ctypes.byref(cls), ctypes.byref(ms),
-                                                 ctypes.byref(cnt), ctypes.byref(fl),
-                                                 ctypes.byref(by)))
-            out[name.value.decode()] = {
-                "class": self.lib.ppo_kernel_class_name(cls.value).decode(), "ms": ms.value,
-                "launches": cnt.value, "flops": fl.value, "bytes": by.value}
-        return out
 
     # ---- A11-A13 -------------------------------------------------------------------------
     def minibatch_grad(self, states, actions, old_logp, adv, vtarget, rows, b: int, grad, loss,

@@ -31,13 +31,17 @@ from . import _lib
 from . import engine as E
 from ._lib import check, ptr
 from .agent import _ACT_NAMES, ExponentialLRFacade, FlatAdam, PPOEngineAgent
-from .engine import _need, _stream
+from .engine import EngineBase, _need, _stream
 from .features import Run
 from .models import _Block, move_to_flat
 
 
-class LSTMEngine:
+class LSTMEngine(EngineBase):
     """One ``ppo_lstm_ctx``: BiLSTM actor + critic shapes, workspace and split-K slabs."""
+
+    _abi = {"destroy": "ppo_lstm_ctx_destroy", "bind": "ppo_lstm_bind_params",
+            "entropy_share": "ppo_lstm_loss_entropy_share", "precision": "ppo_lstm_set_precision",
+            "timing": "ppo_lstm_timing", "timing_kernel": "ppo_lstm_timing_kernel"}
 
     fused = False  # the layered path: no bf16 weight images, no staged records
 
@@ -77,32 +81,8 @@ class LSTMEngine:
         self.precision = "f32"
         self._params = None
 
-    def __del__(self):
-        ctx = getattr(self, "_ctx", None)
-        if ctx is not None and ctx.value:
-            try:
-                self.lib.ppo_lstm_ctx_destroy(ctx)
-            except Exception:  # interpreter shutdown
-                pass
-            self._ctx = None
-
     def param_offsets(self) -> list:
         return list(self._offsets)
-
-    def bind(self, flat_params: torch.Tensor) -> None:
-        _need(flat_params, "flat_params", torch.float32, (self.n_params,), self.device)
-        check(self.lib.ppo_lstm_bind_params(self._ctx, ptr(flat_params)))
-        self._params = flat_params
-
-    def loss_entropy_share(self, share: float) -> None:
-        """Share of the entropy bonus in the LOGGED actor loss (ppo_lstm_loss_entropy_share)."""
-        check(self.lib.ppo_lstm_loss_entropy_share(self._ctx, float(share)))
-
-    def set_precision(self, precision: str) -> None:
-        if precision not in _lib.PREC_CODES:
-            raise ValueError(f"unknown precision {precision!r}; use one of {sorted(_lib.PREC_CODES)}")
-        check(self.lib.ppo_lstm_set_precision(self._ctx, _lib.PREC_CODES[precision]))
-        self.precision = precision
 
     def pack_weights(self) -> None:
         """No bf16 weight images on this path."""
@@ -182,36 +162,6 @@ class LSTMEngine:
         if enable is not None:
             check(self.lib.ppo_lstm_fused_step(self._ctx, int(bool(enable))))
         return bool(self.lib.ppo_lstm_fused_step(self._ctx, -1))
-
-    # ---- measurement (the Engine.timing* contract of bench.py) ----------------------------------
-    def timing(self, enable: bool, capacity: int = 65536) -> None:
-        check(self.lib.ppo_lstm_timing(self._ctx, int(enable), int(capacity)))
-
-    def timing_kernels(self) -> dict:
-        out = {}
-        n_k = self.lib.ppo_lstm_timing_kernel(self._ctx, -1, None, None, None, None, None, None)
-        check(min(n_k, 0))
-        for i in range(n_k):
-            name, cls = ctypes.c_char_p(), ctypes.c_int()
-            ms, fl, by = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
-            cnt = ctypes.c_int64()
-            check(self.lib.ppo_lstm_timing_kernel(self._ctx, i, ctypes.byref(name),
-                                                  ctypes.byref(cls), ctypes.byref(ms),
-                                                  ctypes.byref(cnt), ctypes.byref(fl),
-                                                  ctypes.byref(by)))
-            out[name.value.decode()] = {
-                "class": self.lib.ppo_kernel_class_name(cls.value).decode(), "ms": ms.value,
-                "launches": cnt.value, "flops": fl.value, "bytes": by.value}
-        return out
-
-    def timing_read(self) -> dict:
-        out = {}
-        for name, k in self.timing_kernels().items():
-            c = out.setdefault(k["class"], {"ms": 0.0, "launches": 0, "flops": 0.0, "bytes": 0.0})
-            for key in ("ms", "launches", "flops", "bytes"):
-                c[key] += k[key]
-        return out
-
 
 class EngineLSTMActor(nn.Module):
     """models/lstm/lstm_actor.py:9-38 (parameters only; forward through the engine)."""
