@@ -187,6 +187,11 @@ int ppo_perm_to_rows(const int64_t *perm_d, int64_t start, int b, int n_envs, in
 /* Perf-mode shuffle: rows of a keyed bijection (cycle-walking Feistel) of [0, n_envs*t). */
 int ppo_feistel_rows(uint64_t seed, uint64_t epoch, int64_t start, int b, int n_envs, int t,
                      int32_t *rows_d, void *stream);
+/* The same slice [start, start + b) of n_epochs consecutive bijections (epoch0 + y, y <
+ * n_epochs) in one launch: epoch y's rows go to rows_d + y * row_stride (row_stride >= b).  Each
+ * epoch's values are those of ppo_feistel_rows, which is the n_epochs = 1 call. */
+int ppo_feistel_rows_epochs(uint64_t seed, uint64_t epoch0, int n_epochs, int64_t start, int b,
+                            int n_envs, int t, int32_t *rows_d, int64_t row_stride, void *stream);
 
 /* ---- A11-A13: one minibatch loss + gradients -------------------------------------------------
  * replaces ppo.py:109-135 (actor/critic forward, Normal log_prob/entropy, huber critic loss,
@@ -209,8 +214,13 @@ int ppo_minibatch_grad(ppo_ctx *ctx, const float *states_d, const float *actions
  *   ppo_minibatch_grad) into ctx-owned records once per iteration (after GAE, before the epochs;
  *   the first call for a given size allocates and must not be inside a graph capture);
  *   ppo_minibatch_grad_staged(rows_d, b, count_d, ...) is ppo_minibatch_grad on those records.
- *   flags PPO_STAGED_WEIGHTS_CURRENT: the bf16 weight images are already current (the previous
- *   optimizer step was ppo_adam_pack), so the weight refresh is skipped; PPO_STAGED_ROWS_GATHERED:
+ *   flags PPO_STAGED_WEIGHTS_CURRENT: the ctx's images of the parameters are already current
+ *   (the previous optimizer step was ppo_adam_pack / ppo_adam_pack_gather / ppo_update_step_staged,
+ *   or ppo_pack_weights ran after the last change), so the refresh is skipped.  The promise
+ *   covers EVERY parameter of both nets: the bf16 W0 / W1 images and the packed constants image
+ *   (heads, hidden and head biases, log-std and its derived Normal constants), which is all the
+ *   fused kernel reads -- it does not look at the f32 masters;
+ *   PPO_STAGED_ROWS_GATHERED:
  *   the previous step (ppo_adam_pack_gather) gathered rows_d already (count_d must be NULL). */
 #define PPO_STAGED_WEIGHTS_CURRENT 1
 #define PPO_STAGED_ROWS_GATHERED 2
@@ -282,8 +292,9 @@ int ppo_adam_sched(float *p_d, const float *g_d, float *m_d, float *v_d, int64_t
                    float one_minus_beta2, float eps, void *stream);
 
 /* ppo_adam on the ctx's bound parameters (both nets, n_actor = ppo_param_count(ctx, 0)) that
- * also writes the updated W0/W1 into the fused kernels' bf16 weight images (ppo_pack_weights'
- * values), so the next ppo_minibatch_grad_staged may pass PPO_STAGED_WEIGHTS_CURRENT.  sched_d
+ * also writes every updated parameter into the fused kernels' images (the bf16 W0 / W1 images and
+ * the packed constants image; ppo_pack_weights' values), so the next ppo_minibatch_grad_staged may
+ * pass PPO_STAGED_WEIGHTS_CURRENT.  sched_d
  * (nullable) as ppo_adam_sched; NULL -> the three host scalars.  Fused bf16 path only. */
 int ppo_adam_pack(ppo_ctx *ctx, const float *g_d, float *m_d, float *v_d, const float *sched_d,
                   float neg_step_actor, float neg_step_critic, float bc2_sqrt,
@@ -324,6 +335,12 @@ int ppo_ctx_timing_kernel(ppo_ctx *ctx, int index, const char **name, int *kclas
  * (2 nets, G workgroups, 11) uint64 cycle sums to host_out (up to max_values) and returns the
  * number of values, then restores the product kernel.  ReLU networks only. */
 int ppo_ctx_phase_stamps(ppo_ctx *ctx, int enable, uint64_t *host_out, int max_values);
+/* Diagnostics / tests: the first `bytes` bytes of net's (0 actor, 1 critic) packed constants image
+ * -- the fused update kernel's per-launch LDS constants in their LDS layout: bf16 head image
+ * [16][H + 8], f32 b0[H], b1[H], f32 [80] (b_h, log-std, log std, 1/var, 1/(2 var); 16 each), the
+ * swizzled bf16 W0 image [H][32] and bf16 W_h^T [H][16] -- copied to host_out after a device
+ * synchronize.  Returns the image's size in bytes (host_out NULL: the size only), < 0 on error. */
+int ppo_ctx_fused_constants(ppo_ctx *ctx, int net, void *host_out, int64_t bytes);
 
 /* ---- harness: synthetic VecEnv dynamics on device + Philox normals ---------------------------
  * The bench/test environment (physics is out of scope): obs' = base_obs + 0.1*a[:, o % A],

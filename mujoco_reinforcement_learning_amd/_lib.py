@@ -112,6 +112,9 @@ _SIGNATURES = {
                                  c_void_p, c_void_p]),
     "ppo_feistel_rows": (c_int, [c_uint64, c_uint64, c_int64, c_int, c_int, c_int, c_void_p,
                                  c_void_p]),
+    "ppo_feistel_rows_epochs": (c_int, [c_uint64, c_uint64, c_int, c_int64, c_int, c_int, c_int,
+                                        c_void_p, c_int64, c_void_p]),
+    "ppo_ctx_fused_constants": (c_int, [c_void_p, c_int, c_void_p, c_int64]),
     "ppo_minibatch_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_int, c_void_p, c_float, c_float, c_float, c_float,
                                    c_float, c_void_p, c_void_p, c_void_p]),

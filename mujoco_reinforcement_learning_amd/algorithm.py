@@ -390,9 +390,8 @@ class PPOEngine:
             self._tg_sched = torch.empty(steps, 4, dtype=torch.float32, device=dev)
             self._tg_graph = None
             self._tg_warm = False
-        for epoch in range(epochs):
-            E.feistel_rows(self._seed() + 7919 * self.dp.rank, self.iteration * epochs + epoch, 0,
-                           batches * b, n, t_len, self._tg_rows[epoch])
+        E.feistel_rows_epochs(self._seed() + 7919 * self.dp.rank, self.iteration * epochs, 0,
+                              batches * b, n, t_len, self._tg_rows)
         self._tg_sched.copy_(sched, non_blocking=True)
 
         staged = eng.fused

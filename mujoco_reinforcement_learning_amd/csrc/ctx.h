@@ -50,6 +50,7 @@ struct ppo_ctx {
   bool fused_ok;                // network shapes the fused kernel supports
   int fused_hidden;
   __bf16 *fw[2][3];             // per net: bf16 W0 image (H, 32), W1 (H, H), W1^T (H, H)
+  char *fconst[2];              // per net: the packed constants image (fused_update.h ConstImgMap)
   __bf16 *fxb;                  // (max_rows, 32) staged bf16 states
   float *fsrow;                 // (max_rows, 16) staged row scalars
   float *fslabs;                // (kFusedMaxWG, total_params) partial gradients

@@ -22,7 +22,27 @@ constexpr int kFusedMaxWG = 128;    // workgroups (= partial-gradient slabs) per
 // drained), and the body's s_memrealtime ticks (100 MHz) for the cycle -> time calibration
 constexpr int kStampSlots = 13;
 
+// One net's packed constants image (ctx->fconst[z]): the fused update kernel's per-launch LDS
+// constants -- bf16 head image, f32 hidden biases, the f32 head-bias / log-std block, and for the
+// ReLU kernels the swizzled W0 image and W_h^T -- byte for byte in their LDS layout
+// (fused_update.hip ConstImage), so the kernel's prologue is a straight copy.  Every writer of
+// the bf16 weight images also stores here, through the one mapping flat parameter index -> image
+// bytes that these offsets drive (const_image_store); the pads are written once at allocation.
+struct ConstImgMap {
+  char *img;                    // null: no image (not the fused path)
+  int64_t begin, end;           // the net's flat parameter range
+  int64_t off_w0, off_b0, off_w1, off_b1, off_wh, off_bh;  // flat offsets (b: -1 = none)
+  int64_t off_logstd;           // actor; -1 for the critic
+  int nh, din;                  // real head count (act_dim / 1), layer-0 input width
+  __bf16 *w0b;                  // the net's row-major global W0 image (H, 32), written with W0
+};
+int64_t fused_const_bytes(int hidden);
+// the image of all-zero parameters without log-std (host buffer of fused_const_bytes(hidden)
+// bytes): every pad at its fixed value
+void fused_const_pads(int hidden, char *host_img);
+
 struct FusedNet {
+  const char *fconst;  // the net's packed constants image (ConstImgMap::img)
   const __bf16 *w0b;   // (H, 32)  bf16(W0), input columns >= din zero
   const __bf16 *w1b;   // (H, H)   bf16(W1)
   const __bf16 *w1bt;  // (H, H)   bf16(W1)^T
@@ -66,9 +86,10 @@ struct AdamPackArgs {
   const float *sched;          // device (neg_step_actor, neg_step_critic, bc2_sqrt), or null
   float neg_a, neg_c, bc2;     // host scalars when sched is null
   float w1, b2, omb2, eps;
-  __bf16 *w0b[2], *w1b[2], *w1bt[2];
-  int64_t off_w0[2], off_w1[2];
+  __bf16 *w1b[2], *w1bt[2];
+  int64_t off_w1[2];
   int din, H;
+  ConstImgMap cmap[2];         // everything outside W1: the W0 images, heads, biases, log-std
 };
 int adam_pack_launch(const AdamPackArgs &a, const TimRec &rec, hipStream_t st);
 
@@ -115,6 +136,8 @@ struct FusedArgs {
   // itself, one chunk ahead -- no gathered xb / srow copy is written or read
   bool direct;
   bool pack_w;                 // prep also refreshes the bf16 weight images from the masters
+  const float *params;         // pack_w: the flat f32 parameters, and the constants images'
+  ConstImgMap cmap[2];         //         maps (refreshed with the weight images)
   int b, din, act_dim, act, hidden;
   float omv;
   LossCoef coef;

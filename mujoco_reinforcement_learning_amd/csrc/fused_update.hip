@@ -42,6 +42,182 @@ using namespace fu;
 
 __device__ __forceinline__ uint16_t bf16_bits(float x) { return static_cast<uint16_t>(pack2(x, 0.f) & 0xffffu); }
 
+// The fused update kernel's LDS layout (the kernel itself is further down; the weight-image
+// writers need the constants' offsets).
+template <int H, bool F32A2>
+struct Lds {
+  static constexpr int PITCH = 2 * H;          // A1 / D2 / A2 / D1 bf16 row pitch (bytes), multiple of 256
+  static constexpr int A2P = 4 * H + 16;       // A2F f32 row pitch (bytes): +16 B -> conflict-free b128 stores
+  static constexpr int WHB = 0;                                 // bf16 head image [16][H + 8]
+  static constexpr int BIAS = WHB + HeadImg<H>::BYTES;          // f32 b0[H], b1[H]
+  static constexpr int X = BIAS + 2 * H * 4;                    // bf16 [64][32]
+  static constexpr int A1 = X + R * 64;                         // bf16 [64][H]
+  static constexpr int D2 = A1 + R * PITCH;                     // bf16 [64][H]
+  // a2 after the layer-1 epilogue: the bf16 image (ReLU: act' needs only the sign it keeps) or
+  // the f32 values (tanh / ELU: act'(a2) on the f32 a2, the head operands rounded on the fly);
+  // the D1 image (bf16) takes the region over after phase 5
+  static constexpr int A2 = D2 + R * PITCH;
+  static constexpr int A2BYTES = F32A2 ? R * A2P : R * PITCH;
+  static constexpr int DZ = A2 + A2BYTES;                       // bf16 dz [64][16]
+  static constexpr int DZT = DZ + R * kDzRowBytes;              // bf16 dz^T [16][64 + 8]
+  static constexpr int HS = DZT + 16 * kDzTPitch;               // f32 head bias, logstd, log std, 1/var, 1/(2 var) [16] each
+  static constexpr int SROW = HS + 80 * 4;                      // f32 [64][16] the chunk's row scalars
+  static constexpr int RED = SROW;                              // epilogue: f32 [8 waves][16 heads][4]
+  // ReLU: the W0 image (H x 32 bf16, x_off-swizzled 64-B rows) LDS-resident for the whole kernel
+  // (the tanh / ELU instantiations, with their f32 a2 region, read it from L2)
+  static constexpr int W0 = SROW + R * kFusedSP * 4;
+  // ReLU: W_h^T as a bf16 [H][16] image (32-B rows): the d2 product's A fragment is one 16-B read
+  // (head_t_frag gathers it from the head image with 8 two-byte reads otherwise)
+  static constexpr int WHT = W0 + (F32A2 ? 0 : H * 64);
+  // ReLU, deferred dW0 (SCHED bit 0): the previous chunk's X image stays resident while the next
+  // one is staged (the two buffers alternate chunk by chunk)
+  static constexpr int X2 = WHT + (F32A2 ? 0 : H * 32);
+  static constexpr int TOTAL = X2 + (F32A2 ? 0 : R * 64);
+  static_assert(TOTAL <= 163840, "LDS budget");
+  static_assert(R * PITCH <= A2BYTES, "D1 image must fit in the a2 region");
+};
+
+// ============================================================================================
+// The packed constants image (fused_update.h ConstImgMap): the LDS regions the kernel's prologue
+// used to build from the f32 parameters in every workgroup of every launch, kept in global memory
+// in their LDS layout.  ONE table -- (LDS offset, image offset, bytes) per linear run -- places
+// both the writers' stores and the prologue's copy.  Run 2 (ReLU kernels only) comes last, so the
+// tanh / ELU kernels copy a prefix; the image offsets do not depend on the activation.
+// ============================================================================================
+struct ConstRun {
+  int lds, img, bytes;
+};
+template <int H, bool F32A2>
+struct ConstImage {
+  using L = Lds<H, F32A2>;
+  static constexpr int B0 = L::X - L::WHB;      // head image, b0, b1
+  static constexpr int B1 = L::SROW - L::HS;    // b_h, log-std, log(std), 1/var, 1/(2 var)
+  static constexpr int B2 = L::X2 - L::W0;      // ReLU: swizzled W0 image, W_h^T
+  static constexpr int NRUN = F32A2 ? 2 : 3;
+  static constexpr ConstRun run[3] = {{L::WHB, 0, B0}, {L::HS, B0, B1}, {L::W0, B0 + B1, B2}};
+  static constexpr int BYTES = B0 + B1 + B2;    // what the kernel copies
+  static constexpr int UNITS = BYTES / 16;
+  static_assert(B0 % 16 == 0 && B1 % 16 == 0 && B2 % 16 == 0 && L::WHB % 16 == 0 &&
+                    L::HS % 16 == 0 && L::W0 % 16 == 0,
+                "the runs are copied in 16-B units");
+  // image offset of the LDS field at `lds_off` (inside run k)
+  static constexpr int at(int k, int lds_off) { return run[k].img + (lds_off - run[k].lds); }
+  // the prologue's copy: 1 KB pieces (one 16-B LDS-DMA load per lane of a wave), run by run
+  static constexpr int pieces(int k) { return (run[k].bytes + 1023) / 1024; }
+  static constexpr int PIECES = pieces(0) + pieces(1) + (NRUN > 2 ? pieces(2) : 0);
+};
+// the writers' offsets: the ReLU layout's image (all three runs)
+template <int H>
+struct ConstOff {
+  using C = ConstImage<H, false>;
+  using L = Lds<H, false>;
+  static constexpr int WHB = C::at(0, L::WHB), BIAS = C::at(0, L::BIAS), HS = C::at(1, L::HS),
+                       W0 = C::at(2, L::W0), WHT = C::at(2, L::WHT), BYTES = C::BYTES;
+  static_assert(ConstImage<H, true>::at(0, Lds<H, true>::BIAS) == BIAS &&
+                    ConstImage<H, true>::at(1, Lds<H, true>::HS) == HS &&
+                    ConstImage<H, true>::BYTES == W0,
+                "the tanh / ELU kernels copy a prefix of the same image");
+};
+constexpr int kConstH = 256;  // the compiled width (fused_width_ok)
+
+// log-std -> the per-head Normal constants log(std), 1/var, 1/(2 var); std = exp(logstd)
+struct NormalConst {
+  float log_sd, inv_var, inv_2var;
+};
+__device__ __forceinline__ NormalConst normal_const(float logstd) {
+  const float sd = expf(logstd);
+  const float var = sd * sd;
+  return NormalConst{logf(sd), 1.f / var, 1.f / (2.f * var)};
+}
+
+// Parameters i .. i + N - 1 of the flat vector now hold p[]: their bytes of net m's constants
+// image (and, for W0, of its row-major global bf16 image m.w0b).  N = 1, or N = 4 with i % 4 == 0: every tensor starts 64-B aligned in the flat layout,
+// so such a group lies in one tensor (and, past its end, in the layout's padding) and is placed
+// with one pass over the tensor ranges, in 32-bit offsets from the net's first parameter.  W1 has
+// no bytes here; a parameter outside the net, or in a pad, stores nothing.
+template <int H, int N>
+__device__ __forceinline__ void const_image_store(const ConstImgMap &m, int64_t i, const float (&p)[N]) {
+  using O = ConstOff<H>;
+  static_assert(N == 1 || N == 4, "one parameter, or an aligned group of four");
+  if (m.img == nullptr || i < m.begin || i >= m.end) return;
+  char *const img = m.img;
+  const int r = static_cast<int>(i - m.begin);
+  const auto rel = [&](int64_t off) { return off < 0 ? INT32_MIN / 2 : static_cast<int>(off - m.begin); };
+  int e = r - rel(m.off_w1);
+  if (e >= 0 && e < H * H) return;
+  e = r - rel(m.off_w0);
+  if (e >= 0 && e < H * m.din) {  // W0[f][k]: the x_off-swizzled 64-B rows
+    int f = e / m.din, k = e - f * m.din;
+    uint16_t *const w0b = reinterpret_cast<uint16_t *>(m.w0b);
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const uint16_t hb = bf16_bits(p[j]);
+      *reinterpret_cast<uint16_t *>(img + O::W0 + x_off(f, k >> 3) + 2 * (k & 7)) = hb;
+      if (w0b) w0b[f * kFusedKX + k] = hb;  // the row-major global W0 image
+      if (++k == m.din) k = 0, ++f;
+    }
+    return;
+  }
+  e = r - rel(m.off_wh);
+  if (e >= 0 && e < m.nh * H) {  // W_h[a][f]: the head image and its transpose (H % 4 == 0)
+    const int a = e / H, f = e % H;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const uint16_t hb = bf16_bits(p[j]);
+      *reinterpret_cast<uint16_t *>(img + O::WHB + a * HeadImg<H>::PITCH + 2 * (f + j)) = hb;
+      *reinterpret_cast<uint16_t *>(img + O::WHT + 2 * ((f + j) * 16 + a)) = hb;
+    }
+    return;
+  }
+  float *const bias = reinterpret_cast<float *>(img + O::BIAS);
+  float *const hs = reinterpret_cast<float *>(img + O::HS);
+  e = r - rel(m.off_b0);
+  if (e >= 0 && e < H) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) bias[e + j] = p[j];
+    return;
+  }
+  e = r - rel(m.off_b1);
+  if (e >= 0 && e < H) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) bias[H + e + j] = p[j];
+    return;
+  }
+  e = r - rel(m.off_bh);
+  if (e >= 0 && e < m.nh) {
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+      if (e + j < m.nh) hs[e + j] = p[j];
+    return;
+  }
+  e = r - rel(m.off_logstd);
+  if (e >= 0 && e < m.nh) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      if (e + j >= m.nh) continue;
+      const NormalConst c = normal_const(p[j]);
+      hs[16 + e + j] = p[j];
+      hs[32 + e + j] = c.log_sd;
+      hs[48 + e + j] = c.inv_var;
+      hs[64 + e + j] = c.inv_2var;
+    }
+  }
+}
+
+int64_t fused_const_bytes(int) { return ConstOff<kConstH>::BYTES; }
+
+void fused_const_pads(int, char *host_img) {
+  using O = ConstOff<kConstH>;
+  for (int i = 0; i < O::BYTES; ++i) host_img[i] = 0;
+  // a head without a log-std (the actor's heads >= act_dim, all of the critic's) has std = 1:
+  // log(std) = 0, 1/var = 1, 1/(2 var) = 0.5; the actor's real heads are overwritten
+  float *hs = reinterpret_cast<float *>(host_img + O::HS);
+  for (int a = 0; a < 16; ++a) {
+    hs[48 + a] = 1.f;
+    hs[64 + a] = 0.5f;
+  }
+}
+
 // ============================================================================================
 // Prep: gather the minibatch rows once per minibatch into contiguous bf16 / f32 staging, and
 // refresh the bf16 weight images (row-major and transposed W1) from the f32 masters.
@@ -101,7 +277,25 @@ __global__ __launch_bounds__(256) void fused_prep_kernel(FusedArgs q, int row_bl
   const int H = q.hidden;
   const int64_t per_net = static_cast<int64_t>(H) * kFusedKX + static_cast<int64_t>(H) * H;
   const int64_t e = static_cast<int64_t>(blockIdx.x - row_blocks) * 256 + tid;
-  if (e >= 2 * per_net) return;
+  if (e >= 2 * per_net) {
+    // the constants images: every parameter of the two nets outside their W1 blocks
+    int64_t c = e - 2 * per_net;
+    for (int z = 0; z < 2; ++z) {
+      const ConstImgMap &m = q.cmap[z];
+      const int64_t w1_end = m.off_w1 + static_cast<int64_t>(H) * H;
+      const int64_t n_lo = m.off_w1 - m.begin, n_hi = m.end - w1_end;
+      if (c < n_lo + n_hi) {
+        const int64_t i = c < n_lo ? m.begin + c : w1_end + (c - n_lo);
+        const float pv[1] = {q.params[i]};
+        ConstImgMap mc = m;
+        mc.w0b = nullptr;  // the weight threads above write it, with its zero pad columns
+        const_image_store<kConstH>(mc, i, pv);
+        return;
+      }
+      c -= n_lo + n_hi;
+    }
+    return;
+  }
   const int z = e >= per_net;
   const FusedNet &N = z ? q.net[1] : q.net[0];
   const int64_t i = e - z * per_net;
@@ -229,14 +423,9 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(AdamPackArgs a, int gen_
     a.p[i] = p;
     a.m[i] = m;
     a.v[i] = v;
+    const float pv1[1] = {p};
 #pragma unroll
-    for (int z = 0; z < 2; ++z) {
-      const int64_t e = i - a.off_w0[z];
-      if (e >= 0 && e < static_cast<int64_t>(H) * a.din) {
-        const int f = static_cast<int>(e / a.din), k = static_cast<int>(e % a.din);
-        reinterpret_cast<uint16_t *>(a.w0b[z])[f * kFusedKX + k] = bf16_bits(p);
-      }
-    }
+    for (int z = 0; z < 2; ++z) const_image_store<kConstH>(a.cmap[z], i, pv1);
     return;
   }
   __shared__ uint16_t tile[kPackTile][kPackTile + 2];
@@ -310,15 +499,9 @@ __device__ __forceinline__ void adam_apply(const AdamPackArgs &a, int64_t i, flo
       uint16_t *wt = reinterpret_cast<uint16_t *>(a.w1bt[z]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) wt[w_frag(c + e, o, H)] = bf16_bits(pv[e]);
+      continue;  // a 4-group that starts in W1 ends in it (H * H % 4 == 0, 64-B aligned tensors)
     }
-    const int64_t e0 = i - a.off_w0[z];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (e0 + e >= 0 && e0 + e < static_cast<int64_t>(H) * a.din) {
-        const int f = static_cast<int>((e0 + e) / a.din), k = static_cast<int>((e0 + e) % a.din);
-        reinterpret_cast<uint16_t *>(a.w0b[z])[f * kFusedKX + k] = bf16_bits(pv[e]);
-      }
-    }
+    const_image_store<kConstH>(a.cmap[z], i, pv);  // W0's two images, heads, biases, log-std
   }
 }
 
@@ -430,40 +613,6 @@ __global__ __launch_bounds__(G * kRedChunks) void step_tail_kernel(ReduceArgs r,
 // ============================================================================================
 // The fused update kernel
 // ============================================================================================
-template <int H, bool F32A2>
-struct Lds {
-  static constexpr int PITCH = 2 * H;          // A1 / D2 / A2 / D1 bf16 row pitch (bytes), multiple of 256
-  static constexpr int A2P = 4 * H + 16;       // A2F f32 row pitch (bytes): +16 B -> conflict-free b128 stores
-  static constexpr int WHB = 0;                                 // bf16 head image [16][H + 8]
-  static constexpr int BIAS = WHB + HeadImg<H>::BYTES;          // f32 b0[H], b1[H]
-  static constexpr int X = BIAS + 2 * H * 4;                    // bf16 [64][32]
-  static constexpr int A1 = X + R * 64;                         // bf16 [64][H]
-  static constexpr int D2 = A1 + R * PITCH;                     // bf16 [64][H]
-  // a2 after the layer-1 epilogue: the bf16 image (ReLU: act' needs only the sign it keeps) or
-  // the f32 values (tanh / ELU: act'(a2) on the f32 a2, the head operands rounded on the fly);
-  // the D1 image (bf16) takes the region over after phase 5
-  static constexpr int A2 = D2 + R * PITCH;
-  static constexpr int A2BYTES = F32A2 ? R * A2P : R * PITCH;
-  static constexpr int DZ = A2 + A2BYTES;                       // bf16 dz [64][16]
-  static constexpr int DZT = DZ + R * kDzRowBytes;              // bf16 dz^T [16][64 + 8]
-  static constexpr int HS = DZT + 16 * kDzTPitch;               // f32 head bias, logstd, log std, 1/var, 1/(2 var) [16] each
-  static constexpr int SROW = HS + 80 * 4;                      // f32 [64][16] the chunk's row scalars
-  static constexpr int RED = SROW;                              // epilogue: f32 [8 waves][16 heads][4]
-  // ReLU: the W0 image (H x 32 bf16, x_off-swizzled 64-B rows) LDS-resident for the whole kernel
-  // (the tanh / ELU instantiations, with their f32 a2 region, read it from L2)
-  static constexpr int W0 = SROW + R * kFusedSP * 4;
-  // ReLU: W_h^T as a bf16 [H][16] image (32-B rows): the d2 product's A fragment is one 16-B read
-  // (head_t_frag gathers it from the head image with 8 two-byte reads otherwise)
-  static constexpr int WHT = W0 + (F32A2 ? 0 : H * 64);
-  // ReLU, deferred dW0 (SCHED bit 0): the previous chunk's X image stays resident while the next
-  // one is staged (the two buffers alternate chunk by chunk)
-  static constexpr int X2 = WHT + (F32A2 ? 0 : H * 32);
-  static constexpr int TOTAL = X2 + (F32A2 ? 0 : R * 64);
-  static_assert(TOTAL <= 163840, "LDS budget");
-  static_assert(R * PITCH <= A2BYTES, "D1 image must fit in the a2 region");
-};
-
-
 // 8 f32 (two float4) -> the bf16x8 MFMA operand (RNE), for the f32-a2 (tanh / ELU) instantiations
 __device__ __forceinline__ bf16x8 pack8(float4 u, float4 v) {
   const uint4 p = make_uint4(pack2(u.x, u.y), pack2(u.z, u.w), pack2(v.x, v.y), pack2(v.z, v.w));
@@ -571,35 +720,35 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
     t_real0 = __builtin_amdgcn_s_memrealtime();
     __builtin_amdgcn_s_waitcnt(0xC07F);
   }
-  stage_head_image<H>(whb, N.wh, ACTOR ? A : 1, tid, NT);
-  for (int i = tid; i < 2 * H; i += NT) {
-    const float *b = i < H ? N.b0 : N.b1;
-    (reinterpret_cast<float *>(lds + L::BIAS))[i] = b ? b[i % H] : 0.f;
-  }
-  if (tid < 32) {
-    const int a = tid & 15;
-    const bool ok = a < (ACTOR ? A : 1);
-    (reinterpret_cast<float *>(lds + L::HS))[tid] =
-        tid < 16 ? ((ok && N.bh) ? N.bh[a] : 0.f) : ((ACTOR && ok) ? q.logstd[a] : 0.f);
-  }
-  if (tid < 16) {  // per-head Normal constants: log(std), 1/var, 1/(2 var); std = exp(logstd)
-    const bool ok = ACTOR && tid < A;
-    const float sd = ok ? expf(q.logstd[tid]) : 1.f;
-    const float var = sd * sd;
-    (reinterpret_cast<float *>(lds + L::HS))[32 + tid] = ok ? logf(sd) : 0.f;
-    (reinterpret_cast<float *>(lds + L::HS))[48 + tid] = 1.f / var;
-    (reinterpret_cast<float *>(lds + L::HS))[64 + tid] = 1.f / (2.f * var);
-  }
-  if constexpr (!F32A2) {
-    for (int i = tid; i < H * 4; i += NT) {  // 16-B chunk (row i / 4, chunk i % 4) of W0
-      const uint4 v = reinterpret_cast<const uint4 *>(N.w0b)[i];
-      *reinterpret_cast<uint4 *>(lds + L::W0 + x_off(i >> 2, i & 3)) = v;
-    }
-    const int nh_real = ACTOR ? A : 1;
-    for (int i = tid; i < H * 16; i += NT) {  // W_h^T[f][a] = bf16(W_h[a][f]), heads >= A zero
-      const int a = i / H, f = i % H;           // coalesced reads of W_h's rows
-      const float v = a < nh_real ? N.wh[a * H + f] : 0.f;
-      *reinterpret_cast<uint16_t *>(lds + L::WHT + 2 * (f * 16 + a)) = bf16_bits(v);
+  // The per-launch constants -- head image, hidden biases, head bias / log-std block and, ReLU,
+  // the W0 image and W_h^T -- are one straight copy of the net's packed image (ConstImage) by
+  // LDS-DMA (16 B a lane, no data registers): wave w moves the 1 KB pieces w, w + 8, ... of the
+  // runs (a run's last piece with the lanes past its end off), every load issued before the one
+  // wait below, behind the row-index load above.
+  {
+    using CI = ConstImage<H, F32A2>;
+    typedef __attribute__((address_space(3))) void lds_void;
+    const char *const src = N.fconst;
+#pragma unroll
+    for (int j = 0; j < (CI::PIECES + NW - 1) / NW; ++j) {
+      const int c = w + NW * j;
+      if (CI::PIECES % NW != 0 && c >= CI::PIECES) continue;
+      // piece c = piece cc of run r (wave-uniform)
+      constexpr ConstRun r0 = CI::run[0], r1 = CI::run[1], r2 = CI::run[2];
+      ConstRun r = r0;
+      int cc = c;
+      if (cc >= CI::pieces(0)) {
+        r = r1;
+        cc -= CI::pieces(0);
+        if (CI::NRUN > 2 && cc >= CI::pieces(1)) {
+          r = r2;
+          cc -= CI::pieces(1);
+        }
+      }
+      const int unit = 64 * cc + lane;
+      if (16 * unit < r.bytes)
+        __builtin_amdgcn_global_load_lds(gptr(src + r.img + 16 * unit),
+                                         (lds_void *)(lds + r.lds + 1024 * cc), 16, 0, 0);
     }
   }
   const float *const hbias = reinterpret_cast<const float *>(lds + L::HS);
@@ -613,6 +762,8 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
     for (int i = tid; i < R * 64 / 16; i += NT)
       *reinterpret_cast<uint4 *>(lds + L::X + 16 * i) = make_uint4(0u, 0u, 0u, 0u);
   }
+  // the constants' LDS-DMA writes have landed (lds_sync waits on lgkmcnt only)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   lds_sync();
 
   // ---- persistent accumulators ----
@@ -1165,7 +1316,12 @@ int fused_prep_launch(const FusedArgs &q, const TimRec &rec, hipStream_t st) {
   const int row_blocks = q.rec ? static_cast<int>(ceil_div(static_cast<int64_t>(q.b) * 8, 256))
                                : ceil_div(q.b, 256);
   const int64_t per_net = static_cast<int64_t>(q.hidden) * (kFusedKX + q.hidden);
-  const int w_blocks = q.pack_w ? static_cast<int>(ceil_div(2 * per_net, 256)) : 0;
+  int64_t n_const = 0;  // the parameters outside W1 (the constants images)
+  for (int z = 0; z < 2 && q.pack_w; ++z) {
+    PPO_REQUIRE(q.params && q.cmap[z].img, "fused prep: weight refresh without the constants image");
+    n_const += q.cmap[z].end - q.cmap[z].begin - static_cast<int64_t>(q.hidden) * q.hidden;
+  }
+  const int w_blocks = q.pack_w ? static_cast<int>(ceil_div(2 * per_net + n_const, 256)) : 0;
   if (row_blocks + w_blocks == 0) return 0;
   launch_k(rec, fused_prep_kernel, dim3(row_blocks + w_blocks), dim3(256), 0, st, q, row_blocks);
   PPO_LAUNCHED();
@@ -1214,7 +1370,7 @@ int gae_records_launch(const GaeRecordArgs &g, bool reward_f64, const TimRec &re
 }
 
 int adam_pack_launch(const AdamPackArgs &a, const TimRec &rec, hipStream_t st) {
-  PPO_REQUIRE(a.H % kPackTile == 0 && a.din >= 1 && a.din <= kFusedKX && a.n > 0,
+  PPO_REQUIRE(a.H % kPackTile == 0 && a.H == kConstH && a.din >= 1 && a.din <= kFusedKX && a.n > 0,
               "adam_pack: H=%d din=%d", a.H, a.din);
   const int gen_blocks = static_cast<int>(ceil_div(a.n, 256));
   const int tiles = a.H / kPackTile;
@@ -1253,7 +1409,7 @@ static void mark_interior(const ReduceArgs &r, TailArgs &t, int np) {
 }
 
 int step_tail_launch(const ReduceArgs &r, const TailArgs &t_in, const TimRec &rec, hipStream_t st) {
-  PPO_REQUIRE(t_in.a.H % 4 == 0 && t_in.a.din >= 1 && t_in.a.din <= kFusedKX &&
+  PPO_REQUIRE(t_in.a.H == kConstH && t_in.a.din >= 1 && t_in.a.din <= kFusedKX &&
                   (!t_in.reduce || r.total == t_in.a.n),
               "step tail: H=%d din=%d", t_in.a.H, t_in.a.din);
   constexpr int G = kRedGroups, NT = G * kRedChunks;

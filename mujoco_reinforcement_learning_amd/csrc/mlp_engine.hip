@@ -36,6 +36,7 @@ static void fused_nets(const ppo_ctx *ctx, FusedNet (&out)[2]) {
   for (int z = 0; z < 2; ++z) {
     const NetDesc &nd = ctx->net[z];
     FusedNet &fn = out[z];
+    fn.fconst = ctx->fconst[z];
     fn.w0b = ctx->fw[z][0];
     fn.w1b = ctx->fw[z][1];
     fn.w1bt = ctx->fw[z][2];
@@ -51,6 +52,27 @@ static void fused_nets(const ppo_ctx *ctx, FusedNet (&out)[2]) {
     fn.off_b1 = nd.layer[1].b_off;
     fn.off_wh = nd.layer[2].w_off;
     fn.off_bh = nd.layer[2].b_off;
+  }
+}
+
+// Where each parameter of both nets lands in the packed constants images (fused_update.h).
+static void fused_const_maps(const ppo_ctx *ctx, ConstImgMap (&out)[2]) {
+  for (int z = 0; z < 2; ++z) {
+    const NetDesc &nd = ctx->net[z];
+    ConstImgMap &m = out[z];
+    m.img = ctx->fconst[z];
+    m.begin = nd.begin;
+    m.end = nd.begin + nd.count;
+    m.off_w0 = nd.layer[0].w_off;
+    m.off_b0 = nd.layer[0].b_off;
+    m.off_w1 = nd.layer[1].w_off;
+    m.off_b1 = nd.layer[1].b_off;
+    m.off_wh = nd.layer[2].w_off;
+    m.off_bh = nd.layer[2].b_off;
+    m.off_logstd = z == 0 ? nd.logstd_off : -1;
+    m.nh = z == 0 ? ctx->cfg.act_dim : 1;
+    m.din = ctx->cfg.obs_dim * ctx->cfg.window;
+    m.w0b = ctx->fw[z][0];
   }
 }
 
@@ -81,6 +103,8 @@ static FusedArgs fused_args(ppo_ctx *ctx, const float *states_d, const float *ac
   q.rec = staged ? ctx->frec : nullptr;
   q.n_rec = staged ? ctx->frec_rows : 0;
   q.pack_w = pack_w;
+  q.params = ctx->params;
+  fused_const_maps(ctx, q.cmap);
   q.b = b;
   q.din = ctx->cfg.obs_dim * ctx->cfg.window;
   q.act_dim = ctx->cfg.act_dim;
@@ -219,12 +243,11 @@ static AdamPackArgs adam_pack_args(const ppo_ctx *ctx, const float *g_d, float *
   FusedNet nets[2];
   fused_nets(ctx, nets);
   for (int z = 0; z < 2; ++z) {
-    a.w0b[z] = const_cast<__bf16 *>(nets[z].w0b);
     a.w1b[z] = const_cast<__bf16 *>(nets[z].w1b);
     a.w1bt[z] = const_cast<__bf16 *>(nets[z].w1bt);
-    a.off_w0[z] = nets[z].off_w0;
     a.off_w1[z] = nets[z].off_w1;
   }
+  fused_const_maps(ctx, a.cmap);
   a.din = ctx->cfg.obs_dim * ctx->cfg.window;
   a.H = ctx->fused_hidden;
   return a;
@@ -358,7 +381,8 @@ extern "C" int ppo_ctx_create(const ppo_net_cfg *cfg, int device, ppo_ctx **out)
     ctx->fused_hidden = H;
     if (ctx->fused_ok) {
       const int64_t wimg = align_up(static_cast<int64_t>(H) * (kFusedKX + 2 * H), 128);
-      const int64_t bytes = 2 * wimg * 2 + align_up(R * kFusedKX * 2, 256) +
+      const int64_t cimg = align_up(fused_const_bytes(H), 256);
+      const int64_t bytes = 2 * wimg * 2 + 2 * cimg + align_up(R * kFusedKX * 2, 256) +
                             align_up(R * kFusedSP * 4, 256) +
                             static_cast<int64_t>(kFusedMaxWG) * off * 4 + kFusedMaxWG * 2 * 4 + 1024;
       void *fa = nullptr;
@@ -378,6 +402,25 @@ extern "C" int ppo_ctx_create(const ppo_net_cfg *cfg, int device, ppo_ctx **out)
         ctx->fw[z][1] = wb + static_cast<int64_t>(H) * kFusedKX;
         ctx->fw[z][2] = wb + static_cast<int64_t>(H) * (kFusedKX + H);
         c += wimg * 2;
+      }
+      {  // the constants images, their pads written here once (the writers store parameters only)
+        char *pads = new (std::nothrow) char[fused_const_bytes(H)];
+        e = pads ? hipSuccess : hipErrorOutOfMemory;
+        for (int z = 0; z < 2 && e == hipSuccess; ++z) {
+          ctx->fconst[z] = c;
+          c += cimg;
+          fused_const_pads(H, pads);
+          e = hipMemcpy(ctx->fconst[z], pads, fused_const_bytes(H), hipMemcpyHostToDevice);
+        }
+        delete[] pads;
+        if (e != hipSuccess) {
+          (void)hipFree(fa);
+          (void)hipFree(arena);
+          delete ctx;
+          set_error("ppo_ctx_create: writing the fused constants images failed: %s",
+                    hipGetErrorString(e));
+          return PPO_EHIP;
+        }
       }
       ctx->fxb = reinterpret_cast<__bf16 *>(c);
       c += align_up(R * kFusedKX * 2, 256);
@@ -471,6 +514,8 @@ extern "C" int ppo_pack_weights(ppo_ctx *ctx, void *stream) {
   fused_nets(ctx, q.net);
   q.b = 0;
   q.pack_w = true;
+  q.params = ctx->params;
+  fused_const_maps(ctx, q.cmap);
   q.din = ctx->cfg.obs_dim * ctx->cfg.window;
   q.hidden = ctx->fused_hidden;
   const double H = ctx->fused_hidden;
@@ -967,6 +1012,20 @@ extern "C" int ppo_ctx_phase_stamps(ppo_ctx *ctx, int enable, uint64_t *host_out
     PPO_HIP_TRY(hipMemcpy(host_out, ctx->fstamps, sizeof(uint64_t) * std::min(got, max_values),
                           hipMemcpyDeviceToHost));
   return got;
+}
+
+extern "C" int ppo_ctx_fused_constants(ppo_ctx *ctx, int net, void *host_out, int64_t bytes) {
+  PPO_REQUIRE(ctx != nullptr, "ppo_ctx_fused_constants: null ctx");
+  PPO_REQUIRE(ctx->fused_ok, "ppo_ctx_fused_constants: network shape has no fused kernel");
+  const int64_t size = fused_const_bytes(ctx->fused_hidden);
+  if (!host_out) return static_cast<int>(size);
+  PPO_REQUIRE((net == 0 || net == 1) && bytes >= 0 && bytes <= size,
+              "ppo_ctx_fused_constants: net %d, %lld of %lld bytes", net,
+              static_cast<long long>(bytes), static_cast<long long>(size));
+  PPO_HIP_TRY(hipSetDevice(ctx->device));
+  PPO_HIP_TRY(hipDeviceSynchronize());
+  PPO_HIP_TRY(hipMemcpy(host_out, ctx->fconst[net], bytes, hipMemcpyDeviceToHost));
+  return static_cast<int>(size);
 }
 
 extern "C" int ppo_ctx_set_precision(ppo_ctx *ctx, int prec) {

@@ -482,11 +482,14 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x, uint32_t k) {
   return x;
 }
 
-__global__ void feistel_rows_kernel(uint64_t seed, uint64_t epoch, int64_t start, int b,
+// blockIdx.y = one epoch of the bijection: epoch0 + y, written at rows + y * row_stride.
+__global__ void feistel_rows_kernel(uint64_t seed, uint64_t epoch0, int64_t start, int b,
                                     int n_envs, int t_len, int half_bits,
-                                    int32_t *__restrict__ rows) {
+                                    int32_t *__restrict__ rows, int64_t row_stride) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= b) return;
+  const uint64_t epoch = epoch0 + blockIdx.y;
+  rows += static_cast<int64_t>(blockIdx.y) * row_stride;
   const uint32_t total = static_cast<uint32_t>(n_envs) * static_cast<uint32_t>(t_len);
   const uint32_t hmask = (1u << half_bits) - 1u;
   uint32_t k[4];
@@ -900,9 +903,13 @@ extern "C" int ppo_perm_to_rows(const int64_t *perm_d, int64_t start, int b, int
   return 0;
 }
 
-extern "C" int ppo_feistel_rows(uint64_t seed, uint64_t epoch, int64_t start, int b, int n_envs,
-                                int t, int32_t *rows_d, void *stream) {
+extern "C" int ppo_feistel_rows_epochs(uint64_t seed, uint64_t epoch0, int n_epochs, int64_t start,
+                                       int b, int n_envs, int t, int32_t *rows_d,
+                                       int64_t row_stride, void *stream) {
   PPO_REQUIRE(rows_d && b > 0 && n_envs > 0 && t > 0, "ppo_feistel_rows: bad args");
+  PPO_REQUIRE(n_epochs >= 1 && n_epochs <= 65535 && (n_epochs == 1 || row_stride >= b),
+              "ppo_feistel_rows: %d epochs at row stride %lld (b=%d)", n_epochs,
+              static_cast<long long>(row_stride), b);
   const int64_t total = static_cast<int64_t>(n_envs) * t;
   PPO_REQUIRE(total < (1ll << 30), "ppo_feistel_rows: N*T too large");
   PPO_REQUIRE(start >= 0 && start + b <= total, "ppo_feistel_rows: slice out of range");
@@ -910,11 +917,16 @@ extern "C" int ppo_feistel_rows(uint64_t seed, uint64_t epoch, int64_t start, in
   while ((1ll << bits) < total) ++bits;
   const int half = (bits + 1) / 2;
   FreeTimingScope timing_scope;
-  launch_k(TimRec{KC_PERM, "feistel_rows_kernel", 0.0, 4.0 * b}, feistel_rows_kernel,
-           dim3(ceil_div(b, 256)), dim3(256), 0, as_stream(stream), seed, epoch, start, b, n_envs,
-           t, half, rows_d);
+  launch_k(TimRec{KC_PERM, "feistel_rows_kernel", 0.0, 4.0 * b * n_epochs}, feistel_rows_kernel,
+           dim3(ceil_div(b, 256), n_epochs), dim3(256), 0, as_stream(stream), seed, epoch0, start,
+           b, n_envs, t, half, rows_d, row_stride);
   PPO_LAUNCHED();
   return 0;
+}
+
+extern "C" int ppo_feistel_rows(uint64_t seed, uint64_t epoch, int64_t start, int b, int n_envs,
+                                int t, int32_t *rows_d, void *stream) {
+  return ppo_feistel_rows_epochs(seed, epoch, 1, start, b, n_envs, t, rows_d, 0, stream);
 }
 
 extern "C" int ppo_adam(float *p_d, const float *g_d, float *m_d, float *v_d, int64_t n,

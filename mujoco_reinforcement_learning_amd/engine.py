@@ -214,8 +214,10 @@ class Engine(RngCounterEngine):
                                            _stream(self.device)))
 
     def pack_weights(self) -> None:
-        """Refresh the bf16 weight images of the fused kernels from the bound parameters (after
-        an optimizer step, before a rollout).  No-op outside the fused bf16 path."""
+        """Refresh the fused kernels' images of the bound parameters -- the bf16 W0 / W1 images and
+        the packed constants image (heads, biases, log-std) -- after any change to the parameters
+        that did not go through adam_pack / update_step_staged, and before a rollout.  No-op
+        outside the fused bf16 path."""
         check(self.lib.ppo_pack_weights(self._ctx, _stream(self.device)))
 
     def observe_act(self, window: torch.Tensor, state: torch.Tensor, obs: Optional[torch.Tensor] = None,
@@ -368,6 +370,16 @@ class Engine(RngCounterEngine):
         check(min(n, 0))
         return out[:n].view(2, -1, 13)
 
+    def fused_constants(self, net: int) -> torch.Tensor:
+        """The packed constants image of net 0 (actor) / 1 (critic) as a uint8 host tensor
+        (ppo_ctx_fused_constants: the fused update kernel's per-launch LDS constants)."""
+        size = self.lib.ppo_ctx_fused_constants(self._ctx, int(net), None, 0)
+        check(min(size, 0))
+        out = torch.zeros(size, dtype=torch.uint8)
+        check(min(self.lib.ppo_ctx_fused_constants(self._ctx, int(net),
+                                                   ctypes.c_void_p(out.data_ptr()), size), 0))
+        return out
+
     # ---- A11-A13 -------------------------------------------------------------------------
     def minibatch_grad(self, states, actions, old_logp, adv, vtarget, rows, b: int, grad, loss,
                        clip_lo: float, clip_hi: float, entropy_coef: float, inv_b: float,
@@ -425,8 +437,10 @@ class Engine(RngCounterEngine):
                               entropy_coef: float, inv_b: float, inv_ba: float,
                               count: Optional[torch.Tensor] = None,
                               weights_current: bool = False, rows_gathered: bool = False) -> None:
-        """minibatch_grad on the staged records; weights_current=True skips the bf16 weight
-        refresh (valid right after adam_pack), rows_gathered=True the row gather (the previous
+        """minibatch_grad on the staged records; weights_current=True skips the refresh of the
+        parameter images (valid right after adam_pack or pack_weights: the fused kernel reads
+        every parameter -- weights, heads, biases, log-std -- from those images, not from
+        flat_params), rows_gathered=True the row gather (the previous
         adam_pack(next_rows=rows) did it)."""
         _need(rows, "rows", torch.int32, device=self.device)
         _need(grad, "grad", torch.float32, (self.n_params,), self.device)
@@ -588,6 +602,21 @@ def feistel_rows(seed: int, epoch: int, start: int, b: int, n_envs: int, horizon
     _need(rows, "rows", torch.int32)
     check(lib.ppo_feistel_rows(seed, epoch, int(start), int(b), n_envs, horizon, ptr(rows),
                                _stream(rows.device)))
+
+
+def feistel_rows_epochs(seed: int, epoch0: int, start: int, b: int, n_envs: int, horizon: int,
+                        rows: torch.Tensor) -> None:
+    """feistel_rows for epochs epoch0 .. epoch0 + E - 1 in one launch: rows is (E, >= b) int32
+    with contiguous rows (a row slice of a wider buffer is fine); row e gets epoch epoch0 + e."""
+    lib = _lib.load()
+    _need(rows[0] if rows.dim() == 2 and rows.shape[0] > 0 else rows, "rows", torch.int32)
+    if rows.dim() != 2 or rows.shape[1] < b or rows.stride(1) != 1 or (
+            rows.shape[0] > 1 and rows.stride(0) < b):
+        raise ValueError(f"feistel_rows_epochs: rows must be (E, >= {b}) with unit column stride, "
+                         f"got shape {tuple(rows.shape)} strides {rows.stride()}")
+    check(lib.ppo_feistel_rows_epochs(seed, int(epoch0), int(rows.shape[0]), int(start), int(b),
+                                      n_envs, horizon, ptr(rows), int(rows.stride(0)),
+                                      _stream(rows.device)))
 
 
 def adam(p, g, m, v, n_actor: int, neg_step_actor: float, neg_step_critic: float,
