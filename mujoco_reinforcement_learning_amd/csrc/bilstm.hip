@@ -40,8 +40,10 @@
 #include <vector>
 
 #include "common.h"
+#include "encoder_ctx.h"
 #include "gemm.h"
 #include "gemm_ops.h"
+#include "mlp_ladder.h"
 #include "ppo_loss.h"
 #include "reduce_slabs.h"
 #include "timing.h"
@@ -52,8 +54,6 @@ namespace ppo {
 namespace lstm {
 
 constexpr int kSplits = 32;           // split-K slabs of the weight gradients (at most)
-constexpr int64_t kAlign = 16;        // floats: every flat tensor starts 64-B aligned
-constexpr int64_t kWsAlign = 64;
 
 struct LstmLayer {
   int in;
@@ -62,14 +62,6 @@ struct LstmLayer {
 struct LstmNet {
   int layers, hidden;
   LstmLayer l[PPO_MAX_LAYERS];
-};
-struct MlpLayer {
-  int in, out, act;
-  int64_t w, b;  // b < 0: no bias
-};
-struct Mlp {
-  int n;  // layers incl. the output layer
-  MlpLayer l[PPO_MAX_LAYERS + 1];
 };
 
 // ---- kernels --------------------------------------------------------------------------------
@@ -867,18 +859,10 @@ __global__ __launch_bounds__(256) void lstm_loss_kernel(const float *__restrict_
 using namespace ppo;
 using namespace ppo::lstm;
 
-struct ppo_lstm_ctx {
+struct ppo_lstm_ctx : EncoderCtx {
   ppo_lstm_cfg cfg;
-  int device;
-  int prec;
-  float ent_log_share;  // ppo_*_loss_entropy_share (logged actor loss only)
   LstmNet net[2];  // 0 actor, 1 critic
   Mlp mu, ls, vc;  // actor mean / logstd MLPs, critic MLP
-  int64_t total, n_actor;
-  std::vector<int64_t> offsets;  // torch parameters() order, actor then critic
-  float *params;
-  float *ws;
-  int64_t rows;  // workspace rows
   // workspace views
   float *x;                          // [rows][W*O] gathered states
   float *g[2][PPO_MAX_LAYERS];       // [rows*W][8H]
@@ -902,7 +886,6 @@ struct ppo_lstm_ctx {
   float *slabs;                      // [kSplits][total] (the first `splits` used)
   int splits;                        // weight-gradient split-K slabs (PPO_LSTM_SPLITS)
   float *row_part;                   // [rows][3]
-  int maxw;
   int fused_step;  // bf16 forward steps as lstm_step_fwd_kernel (ppo_lstm_fused_step)
   int rollout;     // inside forward_rollout: the step launches take the rollout kernel
   // forward_all's paired rollout steps: lstm_forward queues each net's step arguments (s > 0)
@@ -910,7 +893,6 @@ struct ppo_lstm_ctx {
   int defer_steps;
   int npend[2];
   StepArgs pend[2][16];
-  Timing tim;
 };
 
 namespace {
@@ -952,81 +934,19 @@ bool feat16_on(const ppo_lstm_ctx *x) {
          (x->cfg.window * 2 * x->cfg.latent) % 4 == 0 && !(v && atoi(v) == 0);
 }
 
-void add_mlp(Mlp &m, int in, const ppo_lstm_cfg &c, int out, int final_act, int64_t &off,
-             std::vector<int64_t> &offs) {
-  m.n = c.n_hidden + 1;
-  for (int l = 0; l < m.n; ++l) {
-    MlpLayer &L = m.l[l];
-    L.in = in;
-    L.out = l < c.n_hidden ? c.hidden[l] : out;
-    L.act = l < c.n_hidden ? c.activation : final_act;
-    L.w = off;
-    offs.push_back(off);
-    off = align_up(off + static_cast<int64_t>(L.in) * L.out, kAlign);
-    if (c.use_bias) {
-      L.b = off;
-      offs.push_back(off);
-      off = align_up(off + L.out, kAlign);
-    } else {
-      L.b = -1;
-    }
-    in = L.out;
-  }
-}
-
-void add_lstm(LstmNet &n, int layers, int in, int h, int64_t &off, std::vector<int64_t> &offs) {
+void add_lstm(LstmNet &n, int layers, int in, int h, ParamLayout &lay) {
   n.layers = layers;
   n.hidden = h;
   for (int l = 0; l < layers; ++l) {
     LstmLayer &L = n.l[l];
     L.in = l == 0 ? in : 2 * h;
     for (int d = 0; d < 2; ++d) {  // nn.LSTM order: w_ih, w_hh, b_ih, b_hh, then _reverse
-      L.w_ih[d] = off;
-      offs.push_back(off);
-      off = align_up(off + 4LL * h * L.in, kAlign);
-      L.w_hh[d] = off;
-      offs.push_back(off);
-      off = align_up(off + 4LL * h * h, kAlign);
-      L.b_ih[d] = off;
-      offs.push_back(off);
-      off = align_up(off + 4LL * h, kAlign);
-      L.b_hh[d] = off;
-      offs.push_back(off);
-      off = align_up(off + 4LL * h, kAlign);
+      L.w_ih[d] = lay.add(4LL * h * L.in);
+      L.w_hh[d] = lay.add(4LL * h * h);
+      L.b_ih[d] = lay.add(4LL * h);
+      L.b_hh[d] = lay.add(4LL * h);
     }
   }
-}
-
-int gemm_fwd(ppo_lstm_ctx *x, const GemmProblem *p, int np, int k, int rows, int max_n, int act,
-             bool b_kn, hipStream_t st) {
-  GemmBatch gb{};
-  for (int i = 0; i < np; ++i) gb.p[i] = p[i];
-  gb.k = k;
-  gb.act = act;
-  gb.prec = x->prec;
-  return b_kn ? gemm_rows_fwd_kn(gb, np, rows, max_n, st)
-              : gemm_rows_fwd_nk(gb, np, rows, max_n, st);
-}
-
-int gemm_dx(ppo_lstm_ctx *x, const GemmProblem *p, int np, int k, int rows, int max_n, int act,
-            hipStream_t st) {
-  GemmBatch gb{};
-  for (int i = 0; i < np; ++i) gb.p[i] = p[i];
-  gb.k = k;
-  gb.act = act;
-  gb.prec = x->prec;
-  return gemm_rows_dx(gb, np, rows, max_n, st);
-}
-
-int gemm_partial(ppo_lstm_ctx *x, const GemmProblem *p, int np, int rows, int max_m, int max_n,
-                 hipStream_t st) {
-  GemmBatch gb{};
-  for (int i = 0; i < np; ++i) gb.p[i] = p[i];
-  gb.k = rows;
-  gb.splits = x->splits;
-  gb.slab_stride = x->total;
-  gb.prec = x->prec;
-  return gemm_wgrad_partial(gb, np, max_m, max_n, st);
 }
 
 // LSTM net z forward over xin [b*W][O] (batch-major rows); fills g/c/y/hp of every layer and the
@@ -1094,7 +1014,7 @@ int lstm_forward(ppo_lstm_ctx *x, int z, const float *xin, const __bf16 *xin16, 
         P.k = x->ldx16;
       }
       if (int rc = wide::run(wide::WK_F32, wb, 2, b * W, 4 * H, 0, st)) return rc;
-    } else if (int rc = gemm_fwd(x, p, 2, L.in, b * W, 4 * H, PPO_ACT_IDENTITY, false, st)) {
+    } else if (int rc = gemm_fwd(x->prec, p, 2, L.in, b * W, 4 * H, PPO_ACT_IDENTITY, false, st)) {
       return rc;
     }
     for (int s = 0; s < W; ++s) {
@@ -1193,7 +1113,7 @@ int lstm_forward(ppo_lstm_ctx *x, int z, const float *xin, const __bf16 *xin16, 
           q[d].m = b;
           q[d].n = 4 * H;
         }
-        if (int rc = gemm_fwd(x, q, 2, H, b, 4 * H, PPO_ACT_IDENTITY, false, st)) return rc;
+        if (int rc = gemm_fwd(x->prec, q, 2, H, b, 4 * H, PPO_ACT_IDENTITY, false, st)) return rc;
       }
       CellArgs a{};
       a.g = x->g[z][l];
@@ -1221,96 +1141,28 @@ int lstm_forward(ppo_lstm_ctx *x, int z, const float *xin, const __bf16 *xin16, 
   return 0;
 }
 
-// MLP forward: m1 (and m2 on the same input, the actor's mean / logstd pair) over in [b][in0]
-// in16 (nullable): the input rows as bf16 (the bf16 actor features), read instead of in
-int mlp_forward(ppo_lstm_ctx *x, const Mlp *m[2], float *const *acts[2], int nm, const float *in,
-                int b, hipStream_t st, const __bf16 *in16 = nullptr) {
-  const float *P = x->params;
-  for (int l = 0; l < m[0]->n; ++l) {
-    GemmProblem p[2] = {};
-    for (int k = 0; k < nm; ++k) {
-      const MlpLayer &L = m[k]->l[l];
-      p[k].a = l == 0 ? in : acts[k][l - 1];
-      if (l == 0) p[k].a16 = in16;
-      p[k].lda = L.in;
-      p[k].b = P + L.w;
-      p[k].ldb = L.in;
-      p[k].c = acts[k][l];
-      p[k].ldc = L.out;
-      p[k].bias = L.b >= 0 ? P + L.b : nullptr;
-      p[k].m = b;
-      p[k].n = L.out;
-    }
-    const MlpLayer &L0 = m[0]->l[l];
-    if (int rc = gemm_fwd(x, p, nm, L0.in, b, L0.out, L0.act, false, st)) return rc;
+// The actor's mean / log-std MLPs on the same features (in16, nullable: those as bf16) as one
+// ladder, or the critic's MLP alone.  Backward: problem 0's feature gradient goes to din,
+// problem 1's to x->tmp (the consumer adds it where it reads din: lstm_backward's dy2).
+MlpLadder mlp_ladder(const ppo_lstm_ctx *x, bool actor, float *din, int64_t ld_din) {
+  MlpLadder q{};
+  q.prec = x->prec;
+  q.params = x->params;
+  if (actor) {
+    const __bf16 *in16 = feat16_on(x) ? x->feat16 : nullptr;
+    q.np = 2;
+    q.p[0] = MlpProblem{&x->mu, x->feat_a, in16, x->act_mu, x->dz[0], din};
+    q.p[1] = MlpProblem{&x->ls, x->feat_a, in16, x->act_ls, x->dz[1], x->tmp};
+  } else {
+    q.np = 1;
+    q.p[0] = MlpProblem{&x->vc, x->feat_c, nullptr, x->act_v, x->dz[2], din};
   }
-  return 0;
-}
-
-// MLP backward from dz (gradient of the output layer's pre-activation, [b][out]); weight grads
-// into the slabs, the input gradient (times act'(input) of the feature activation) into din.
-// in16 (nullable): the input rows as bf16 -- the first layer's weight-gradient B operand and the
-// input gradient's activation-derivative operand
-int mlp_backward(ppo_lstm_ctx *x, const Mlp *m[2], float *const *acts[2], int nm, const float *in,
-                 float *const *pp[2], float *din, int64_t ld_din, int feat_act, int b,
-                 hipStream_t st, bool sum_din = true, const __bf16 *in16 = nullptr) {
-  // pp[k]: the problem's two ping-pong buffers; pp[k][0] holds the output-layer gradient
-  const float *P = x->params;
-  float *cur[2] = {pp[0][0], nm == 2 ? pp[1][0] : nullptr};
-  for (int l = m[0]->n - 1; l >= 0; --l) {
-    GemmProblem p[2] = {};
-    for (int k = 0; k < nm; ++k) {
-      const MlpLayer &L = m[k]->l[l];
-      p[k].a = cur[k];
-      p[k].lda = L.out;
-      p[k].b = l == 0 ? in : acts[k][l - 1];
-      if (l == 0) p[k].b16 = in16;
-      p[k].ldb = L.in;
-      p[k].c = x->slabs + L.w;
-      p[k].ldc = L.in;
-      p[k].colsum = L.b >= 0 ? x->slabs + L.b : nullptr;
-      p[k].m = L.out;
-      p[k].n = L.in;
-    }
-    const MlpLayer &L0 = m[0]->l[l];
-    if (int rc = gemm_partial(x, p, nm, b, L0.out, L0.in, st)) return rc;
-    // dX = (dZ W) * act'(X): for l > 0 into the other ping-pong buffer; l == 0: the features
-    GemmProblem q[2] = {};
-    float *nxt[2] = {nullptr, nullptr};
-    for (int k = 0; k < nm; ++k) {
-      const MlpLayer &L = m[k]->l[l];
-      q[k].a = cur[k];
-      q[k].lda = L.out;
-      q[k].b = P + L.w;
-      q[k].ldb = L.in;
-      if (l > 0) {
-        nxt[k] = pp[k][(cur[k] == pp[k][0]) ? 1 : 0];
-        q[k].c = nxt[k];
-        q[k].ldc = L.in;
-        q[k].aux = acts[k][l - 1];
-      } else {
-        q[k].c = k == 0 ? din : x->tmp;
-        q[k].ldc = ld_din;
-        q[k].aux = in;
-        q[k].aux16 = in16;
-      }
-      q[k].m = b;
-      q[k].n = L.in;
-    }
-    const int act = l > 0 ? m[0]->l[l - 1].act : feat_act;
-    if (int rc = gemm_dx(x, q, nm, L0.out, b, L0.in, act, st)) return rc;
-    // the two actor MLPs read the same features: sum their dX (sum_din = false: the consumer
-    // adds x->tmp where it reads din, lstm_backward's dy2)
-    if (l == 0 && nm == 2 && sum_din) {
-      const int64_t n = static_cast<int64_t>(b) * ld_din;
-      launch_k(TimRec{KC_LSTM, "add_inplace_kernel", 0.0, 0.0}, add_inplace_kernel,
-               dim3(ceil_div(n, 256)), dim3(256), 0, st, din, x->tmp, n);
-      PPO_LAUNCHED();
-    }
-    cur[0] = nxt[0];
-    cur[1] = nxt[1];
-  }
-  return 0;
+  q.slabs = x->slabs;
+  q.splits = x->splits;
+  q.slab_stride = x->total;
+  q.ld_din = ld_din;
+  q.in_act = x->cfg.activation;
+  return q;
 }
 
 // BPTT of LSTM net z given dY of the top layer (actor: full [b*W][2H] in x->dy[0]; critic: the
@@ -1363,7 +1215,7 @@ int lstm_backward(ppo_lstm_ctx *x, int z, const float *xin, const __bf16 *xin16,
             Q.k = 4 * H;
           }
           if (int rc = wide::run(wide::WK_F32, wb, 2, b, H, 0, st)) return rc;
-        } else if (int rc = gemm_fwd(x, p, 2, 4 * H, b, H, PPO_ACT_IDENTITY, true, st)) {
+        } else if (int rc = gemm_fwd(x->prec, p, 2, 4 * H, b, H, PPO_ACT_IDENTITY, true, st)) {
           return rc;
         }
       }
@@ -1437,7 +1289,8 @@ int lstm_backward(ppo_lstm_ctx *x, int z, const float *xin, const __bf16 *xin16,
         if (int rc = wide::run(wide::WK_WGRAD, wb, 2, 4 * H, L.in, b * W, st)) return rc;
       } else {  // stacked layers' f32 inputs: the bf16-source GEMM, bias partials for both
         for (int d = 0; d < 2; ++d) pi[d].colsum2 = x->slabs + L.b_hh[d];
-        if (int rc = gemm_partial(x, pi, 2, b * W, 4 * H, L.in, st)) return rc;
+        if (int rc = gemm_partial(x->prec, pi, 2, b * W, 4 * H, L.in, x->splits, x->total, st))
+          return rc;
       }
       for (int d = 0; d < 2; ++d) {
         wide::WideProblem &Q = wb.p[d];
@@ -1450,8 +1303,10 @@ int lstm_backward(ppo_lstm_ctx *x, int z, const float *xin, const __bf16 *xin16,
       }
       if (int rc = wide::run(wide::WK_WGRAD, wb, 2, 4 * H, H, b * W, st)) return rc;
     } else {
-      if (int rc = gemm_partial(x, pi, 2, b * W, 4 * H, L.in, st)) return rc;
-      if (int rc = gemm_partial(x, ph, 2, b * W, 4 * H, H, st)) return rc;
+      if (int rc = gemm_partial(x->prec, pi, 2, b * W, 4 * H, L.in, x->splits, x->total, st))
+        return rc;
+      if (int rc = gemm_partial(x->prec, ph, 2, b * W, 4 * H, H, x->splits, x->total, st))
+        return rc;
     }
     if (l > 0) {  // dY of the layer below = sum_d dG_d W_ih_d (no activation between layers)
       const int nxt = cur ^ 1;
@@ -1467,7 +1322,8 @@ int lstm_backward(ppo_lstm_ctx *x, int z, const float *xin, const __bf16 *xin16,
         p.ldc = L.in;
         p.m = b * W;
         p.n = L.in;
-        if (int rc = gemm_fwd(x, &p, 1, 4 * H, b * W, L.in, PPO_ACT_IDENTITY, true, st)) return rc;
+        if (int rc = gemm_fwd(x->prec, &p, 1, 4 * H, b * W, L.in, PPO_ACT_IDENTITY, true, st))
+          return rc;
       }
       const int64_t n = static_cast<int64_t>(b) * W * L.in;
       launch_k(TimRec{KC_LSTM, "add_inplace_kernel", 0.0, 0.0}, add_inplace_kernel,
@@ -1479,12 +1335,7 @@ int lstm_backward(ppo_lstm_ctx *x, int z, const float *xin, const __bf16 *xin16,
   return 0;
 }
 
-int check_rows(ppo_lstm_ctx *x, int b) {
-  PPO_REQUIRE(b >= 0 && b <= x->rows, "ppo_lstm: %d rows exceed the workspace (%lld)", b,
-              static_cast<long long>(x->rows));
-  PPO_REQUIRE(x->params != nullptr, "ppo_lstm: parameters not bound (ppo_lstm_bind_params)");
-  return 0;
-}
+int check_rows(const ppo_lstm_ctx *x, int b) { return ctx_check_rows(x, "ppo_lstm", b); }
 
 int forward_all(ppo_lstm_ctx *x, const float *xin, const __bf16 *xin16, int b, hipStream_t st) {
   // the rollout (one-layer nets, W16 step kernels): both nets' projections and first steps, then
@@ -1515,13 +1366,8 @@ int forward_all(ppo_lstm_ctx *x, const float *xin, const __bf16 *xin16, int b, h
              dim3(256), 0, st, a2);
     PPO_LAUNCHED();
   }
-  const Mlp *am[2] = {&x->mu, &x->ls};
-  float *const *aa[2] = {x->act_mu, x->act_ls};
-  if (int rc = mlp_forward(x, am, aa, 2, x->feat_a, b, st, feat16_on(x) ? x->feat16 : nullptr))
-    return rc;
-  const Mlp *cm[2] = {&x->vc, nullptr};
-  float *const *ca[2] = {x->act_v, nullptr};
-  return mlp_forward(x, cm, ca, 1, x->feat_c, b, st);
+  if (int rc = mlp_forward(mlp_ladder(x, true, nullptr, 0), b, st)) return rc;
+  return mlp_forward(mlp_ladder(x, false, nullptr, 0), b, st);
 }
 
 }  // namespace
@@ -1554,171 +1400,101 @@ extern "C" int ppo_lstm_ctx_create(const ppo_lstm_cfg *cfg, int device, ppo_lstm
   x->rollout = 0;
   x->splits = g_lstm_splits;
   const int H = c.latent, W = c.window, O = c.obs_dim, A = c.act_dim;
-  int64_t off = 0;
+  ParamLayout lay{&x->offsets};
   // LSTMActor.parameters(): feature_extractor, actor, actor_logstd (lstm_actor.py:12-38)
-  add_lstm(x->net[0], c.actor_layers, O, H, off, x->offsets);
-  add_mlp(x->mu, W * 2 * H, c, A, PPO_ACT_TANH, off, x->offsets);
-  add_mlp(x->ls, W * 2 * H, c, A, PPO_ACT_TANH, off, x->offsets);
-  x->n_actor = off;
+  add_lstm(x->net[0], c.actor_layers, O, H, lay);
+  add_mlp(x->mu, W * 2 * H, c, A, PPO_ACT_TANH, c.use_bias != 0, lay);
+  add_mlp(x->ls, W * 2 * H, c, A, PPO_ACT_TANH, c.use_bias != 0, lay);
+  x->n_actor = lay.total();
   // LSTMCritic.parameters(): feature_extractor.0 (one layer), network (lstm_critic.py:19-31)
-  add_lstm(x->net[1], 1, O, H, off, x->offsets);
-  add_mlp(x->vc, 2 * H, c, 1, PPO_ACT_IDENTITY, off, x->offsets);
-  x->total = off;
+  add_lstm(x->net[1], 1, O, H, lay);
+  add_mlp(x->vc, 2 * H, c, 1, PPO_ACT_IDENTITY, c.use_bias != 0, lay);
+  x->total = lay.total();
   int maxw = std::max(A, 1);
   for (int l = 0; l < c.n_hidden; ++l) maxw = std::max(maxw, c.hidden[l]);
   x->maxw = maxw;
   const int64_t R = c.max_rows;
   x->rows = R;
-  // workspace carve-out
-  int64_t need = 0;
-  auto take = [&](int64_t n) {
-    const int64_t at = need;
-    need = align_up(need + n, kWsAlign);
-    return at;
-  };
-  const int64_t o_x = take(R * W * O);
-  // bf16 buffers: half the floats; the gathered rows padded to the wide GEMM's 64-deep k-tiles
-  // and 128-row tiles (its A operand reads whole tiles)
-  const int ldx16 = static_cast<int>(align_up(O, 64));
-  const int64_t o_x16 = take(((R * W + 128) * ldx16 + 1) / 2);
-  int64_t o_wih16[2][2];
+  Workspace ws(kWsAlign);
+  ws.take_n(&x->x, R * W * O);
+  // the gathered rows as bf16, padded to the wide GEMM's 64-deep k-tiles and 128-row tiles (its A
+  // operand reads whole tiles)
+  x->ldx16 = static_cast<int>(align_up(O, 64));
+  const int64_t x16_n = (R * W + 128) * x->ldx16, wih16_n = 4LL * H * x->ldx16;
+  ws.take_n(&x->x16, x16_n);
   for (int z = 0; z < 2; ++z)
-    for (int d = 0; d < 2; ++d) o_wih16[z][d] = take((4LL * H * ldx16 + 1) / 2);
-  const int64_t o_p16 = take((x->total + 1) / 2);
-  int64_t o_g[2][PPO_MAX_LAYERS], o_c[2][PPO_MAX_LAYERS], o_y[2][PPO_MAX_LAYERS],
-      o_hp[2][PPO_MAX_LAYERS], o_dg16[2][PPO_MAX_LAYERS], o_hp16[2][PPO_MAX_LAYERS],
-      o_whht16[2][PPO_MAX_LAYERS][2];
+    for (int d = 0; d < 2; ++d) ws.take_n(&x->wih16[z][d], wih16_n);
+  ws.take_n(&x->p16, x->total);
   for (int z = 0; z < 2; ++z)
     for (int l = 0; l < x->net[z].layers; ++l) {
-      o_g[z][l] = take(R * W * 8 * H);
-      o_c[z][l] = take(R * W * 2 * H);
-      o_y[z][l] = take(R * W * 2 * H);
-      o_hp[z][l] = take(R * W * 2 * H);
-      o_dg16[z][l] = take((R + 128) * W * 4 * H);
-      for (int d = 0; d < 2; ++d) o_whht16[z][l][d] = take(2LL * H * H);
-      o_hp16[z][l] = take(R * W * H);
+      ws.take_n(&x->g[z][l], R * W * 8 * H);
+      ws.take_n(&x->c[z][l], R * W * 2 * H);
+      ws.take_n(&x->y[z][l], R * W * 2 * H);
+      ws.take_n(&x->hp[z][l], R * W * 2 * H);
+      ws.take_n(&x->dg16[z][l], (R + 128) * W * 8 * H);
+      for (int d = 0; d < 2; ++d) ws.take_n(&x->whht16[z][l][d], 4LL * H * H);
+      ws.take_n(&x->hp16[z][l], R * W * 2 * H);
     }
-  const int64_t o_gh = take(R * 8 * H), o_dhrec = take(R * 2 * H), o_dcarry = take(R * 2 * H);
-  const int64_t o_dy0 = take(R * W * 2 * H), o_dy1 = take(R * W * 2 * H);
-  const int64_t o_tmp = take(R * std::max<int64_t>(W * 2 * H, maxw));
-  const int64_t o_fa = take(R * W * 2 * H), o_fc = take(R * 2 * H);
-  const int64_t o_f16 = take(R * W * H);
-  int64_t o_mu[PPO_MAX_LAYERS + 1], o_ls[PPO_MAX_LAYERS + 1], o_v[PPO_MAX_LAYERS + 1];
+  ws.take_n(&x->gh, R * 8 * H);
+  ws.take_n(&x->dhrec, R * 2 * H);
+  ws.take_n(&x->dcarry, R * 2 * H);
+  ws.take_n(&x->dy[0], R * W * 2 * H);
+  ws.take_n(&x->dy[1], R * W * 2 * H);
+  ws.take_n(&x->tmp, R * std::max<int64_t>(W * 2 * H, maxw));
+  ws.take_n(&x->feat_a, R * W * 2 * H);
+  ws.take_n(&x->feat_c, R * 2 * H);
+  ws.take_n(&x->feat16, R * W * 2 * H);
   for (int l = 0; l <= c.n_hidden; ++l) {
-    o_mu[l] = take(R * x->mu.l[l].out);
-    o_ls[l] = take(R * x->ls.l[l].out);
-    o_v[l] = take(R * x->vc.l[l].out);
-  }
-  int64_t o_dz[3][2];
-  for (int k = 0; k < 3; ++k)
-    for (int p = 0; p < 2; ++p) o_dz[k][p] = take(R * maxw);
-  const int64_t o_slabs = take(kSplits * x->total);
-  const int64_t o_rp = take(R * 3);
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc(&x->ws, sizeof(float) * std::max<int64_t>(need, 1));
-  if (e != hipSuccess) {
-    set_error("ppo_lstm_ctx_create: hipMalloc(%lld floats) failed: %s",
-              static_cast<long long>(need), hipGetErrorString(e));
-    delete x;
-    return PPO_EHIP;
-  }
-  float *w = x->ws;
-  x->x = w + o_x;
-  x->x16 = reinterpret_cast<__bf16 *>(w + o_x16);
-  x->ldx16 = ldx16;
-  for (int z = 0; z < 2; ++z)
-    for (int d = 0; d < 2; ++d) x->wih16[z][d] = reinterpret_cast<__bf16 *>(w + o_wih16[z][d]);
-  x->p16 = reinterpret_cast<__bf16 *>(w + o_p16);
-  for (int z = 0; z < 2; ++z)
-    for (int l = 0; l < x->net[z].layers; ++l) {
-      x->g[z][l] = w + o_g[z][l];
-      x->c[z][l] = w + o_c[z][l];
-      x->y[z][l] = w + o_y[z][l];
-      x->hp[z][l] = w + o_hp[z][l];
-      x->dg16[z][l] = reinterpret_cast<__bf16 *>(w + o_dg16[z][l]);
-      for (int d = 0; d < 2; ++d)
-        x->whht16[z][l][d] = reinterpret_cast<__bf16 *>(w + o_whht16[z][l][d]);
-      x->hp16[z][l] = reinterpret_cast<__bf16 *>(w + o_hp16[z][l]);
-    }
-  x->gh = w + o_gh;
-  x->dhrec = w + o_dhrec;
-  x->dcarry = w + o_dcarry;
-  x->dy[0] = w + o_dy0;
-  x->dy[1] = w + o_dy1;
-  x->tmp = w + o_tmp;
-  x->feat_a = w + o_fa;
-  x->feat_c = w + o_fc;
-  x->feat16 = reinterpret_cast<__bf16 *>(w + o_f16);
-  for (int l = 0; l <= c.n_hidden; ++l) {
-    x->act_mu[l] = w + o_mu[l];
-    x->act_ls[l] = w + o_ls[l];
-    x->act_v[l] = w + o_v[l];
+    ws.take_n(&x->act_mu[l], R * x->mu.l[l].out);
+    ws.take_n(&x->act_ls[l], R * x->ls.l[l].out);
+    ws.take_n(&x->act_v[l], R * x->vc.l[l].out);
   }
   for (int k = 0; k < 3; ++k)
-    for (int p = 0; p < 2; ++p) x->dz[k][p] = w + o_dz[k][p];
-  x->slabs = w + o_slabs;
+    for (int p = 0; p < 2; ++p) ws.take_n(&x->dz[k][p], R * maxw);
+  ws.take_n(&x->slabs, kSplits * x->total);
+  ws.take_n(&x->row_part, R * 3);
+  if (int rc = workspace_alloc(ws, "ppo_lstm_ctx_create", device, false, &x->ws)) {
+    ppo_lstm_ctx_destroy(x);
+    return rc;
+  }
   // the alignment padding between tensors is never written by a GEMM: zero slabs reduce to 0;
   // the padded bf16 rows / images keep zero pad columns (only their first O are ever written)
-  e = hipMemset(x->slabs, 0, sizeof(float) * kSplits * x->total);
-  if (e == hipSuccess) e = hipMemset(x->x16, 0, sizeof(__bf16) * (R * W + 128) * ldx16);
+  hipError_t e = hipMemset(x->slabs, 0, sizeof(float) * kSplits * x->total);
+  if (e == hipSuccess) e = hipMemset(x->x16, 0, sizeof(__bf16) * x16_n);
   for (int z = 0; z < 2 && e == hipSuccess; ++z)
     for (int d = 0; d < 2 && e == hipSuccess; ++d)
-      e = hipMemset(x->wih16[z][d], 0, sizeof(__bf16) * 4LL * H * ldx16);
+      e = hipMemset(x->wih16[z][d], 0, sizeof(__bf16) * wih16_n);
   if (e != hipSuccess) {
+    ppo_lstm_ctx_destroy(x);
     set_error("ppo_lstm_ctx_create: hipMemset failed: %s", hipGetErrorString(e));
-    (void)hipFree(x->ws);
-    delete x;
     return PPO_EHIP;
   }
-  x->row_part = w + o_rp;
   *out = x;
   return 0;
 }
 
 extern "C" int ppo_lstm_ctx_destroy(ppo_lstm_ctx *x) {
   if (!x) return 0;
-  (void)timing_enable(x->tim, 0, 0);
-  for (int i = 0; i < 2 * x->tim.capacity; ++i) (void)hipEventDestroy(x->tim.ev[i]);
-  delete[] x->tim.ev;
-  delete[] x->tim.cls;
-  delete[] x->tim.kname;
-  delete[] x->tim.flops;
-  delete[] x->tim.bytes;
-  if (x->ws) (void)hipFree(x->ws);
+  ctx_release(x);
   delete x;
   return 0;
 }
 
 extern "C" int ppo_lstm_param_layout(const ppo_lstm_ctx *x, int64_t *offsets, int max_tensors,
                                      int64_t *total, int64_t *n_actor) {
-  PPO_REQUIRE(x != nullptr, "ppo_lstm_param_layout: null ctx");
-  const int n = static_cast<int>(x->offsets.size());
-  if (offsets)
-    for (int i = 0; i < std::min(n, max_tensors); ++i) offsets[i] = x->offsets[i];
-  if (total) *total = x->total;
-  if (n_actor) *n_actor = x->n_actor;
-  return n;
+  return ctx_param_layout(x, "ppo_lstm_param_layout", offsets, max_tensors, total, n_actor);
 }
 
 extern "C" int ppo_lstm_bind_params(ppo_lstm_ctx *x, float *params_d) {
-  PPO_REQUIRE(x != nullptr && params_d != nullptr, "ppo_lstm_bind_params: null argument");
-  PPO_REQUIRE(reinterpret_cast<uintptr_t>(params_d) % 64 == 0,
-              "ppo_lstm_bind_params: parameter buffer must be 64-B aligned");
-  x->params = params_d;
-  return 0;
+  return ctx_bind_params(x, "ppo_lstm_bind_params", params_d);
 }
 
 extern "C" int ppo_lstm_loss_entropy_share(ppo_lstm_ctx *x, float share) {
-  PPO_REQUIRE(x != nullptr, "ppo_lstm_loss_entropy_share: null ctx");
-  x->ent_log_share = share;
-  return 0;
+  return ctx_loss_entropy_share(x, "ppo_lstm_loss_entropy_share", share);
 }
 
 extern "C" int ppo_lstm_set_precision(ppo_lstm_ctx *x, int prec) {
-  PPO_REQUIRE(x != nullptr, "ppo_lstm_set_precision: null ctx");
-  PPO_REQUIRE(prec == PPO_PREC_F32 || prec == PPO_PREC_BF16, "ppo_lstm_set_precision: %d", prec);
-  x->prec = prec;
-  return 0;
+  return ctx_set_precision(x, "ppo_lstm_set_precision", prec);
 }
 
 // bf16 mode: the LSTM GEMMs read a bf16 copy of the parameters made once per call (the rounding
@@ -1915,21 +1691,12 @@ extern "C" int ppo_lstm_minibatch_grad(ppo_lstm_ctx *x, const float *states_d,
     PPO_LAUNCHED();
   }
   {  // critic: MLP, then BiLSTM (the gradient of h at t = W-1 lands in dy[0])
-    const Mlp *cm[2] = {&x->vc, nullptr};
-    float *const *ca[2] = {x->act_v, nullptr};
-    float *const *pp[2] = {x->dz[2], nullptr};
-    if (int rc = mlp_backward(x, cm, ca, 1, x->feat_c, pp, x->dy[0], 2 * H, c.activation, b, st))
-      return rc;
+    if (int rc = mlp_backward(mlp_ladder(x, false, x->dy[0], 2 * H), b, st)) return rc;
     if (int rc = lstm_backward(x, 1, x->x, x16, b, st)) return rc;
   }
   {  // actor: both MLPs into one feature gradient, then BiLSTM
-    const Mlp *am[2] = {&x->mu, &x->ls};
-    float *const *aa[2] = {x->act_mu, x->act_ls};
-    float *const *pp[2] = {x->dz[0], x->dz[1]};
-    if (int rc = mlp_backward(x, am, aa, 2, x->feat_a, pp, x->dy[0],
-                              static_cast<int64_t>(W) * 2 * H, c.activation, b, st, false,
-                              feat16_on(x) ? x->feat16 : nullptr))
-      return rc;
+    const MlpLadder q = mlp_ladder(x, true, x->dy[0], static_cast<int64_t>(W) * 2 * H);
+    if (int rc = mlp_backward(q, b, st)) return rc;
     if (int rc = lstm_backward(x, 0, x->x, x16, b, st, x->tmp)) return rc;
   }
   // slabs -> flat gradient, tensor by tensor in a fixed split order
@@ -1961,15 +1728,14 @@ extern "C" int ppo_lstm_minibatch_grad(ppo_lstm_ctx *x, const float *states_d,
 }
 
 extern "C" int ppo_lstm_timing(ppo_lstm_ctx *x, int enable, int capacity) {
-  PPO_REQUIRE(x != nullptr, "ppo_lstm_timing: null ctx");
-  return timing_enable(x->tim, enable, capacity);
+  return ctx_timing(x, "ppo_lstm_timing", enable, capacity);
 }
 
 extern "C" int ppo_lstm_timing_kernel(ppo_lstm_ctx *x, int index, const char **name, int *kclass,
                                       double *total_ms, int64_t *launches, double *flops,
                                       double *bytes) {
-  PPO_REQUIRE(x != nullptr, "ppo_lstm_timing_kernel: null ctx");
-  return timing_read_kernel(x->tim, index, name, kclass, total_ms, launches, flops, bytes);
+  return ctx_timing_kernel(x, "ppo_lstm_timing_kernel", index, name, kclass, total_ms, launches,
+                           flops, bytes);
 }
 
 extern "C" int ppo_lstm_fused_step(ppo_lstm_ctx *x, int enable) {

@@ -27,8 +27,10 @@
 #include "conv.h"
 #include "conv_pixel.h"
 #include "conv_lds.h"
+#include "encoder_ctx.h"
 #include "gemm.h"
 #include "gemm_ops.h"
+#include "mlp_ladder.h"
 #include "ppo_loss.h"
 #include "reduce_slabs.h"
 #include "timing.h"
@@ -41,17 +43,7 @@ using namespace conv;
 constexpr int kMlpSplits = 32;        // split-K slabs of the MLP weight gradients (max)
 constexpr int kConvMaxSplits = 256;   // split-K slabs of a conv weight gradient (max)
 constexpr int kHeadSplits = 256;      // row blocks of the update head (log-std / loss partials)
-constexpr int64_t kAlign = 16;        // floats: every flat tensor starts 64-B aligned
-constexpr int64_t kWsAlign = 64;
 
-struct MlpLayer {
-  int in, out, act;
-  int64_t w, b;  // b < 0: no bias
-};
-struct Mlp {
-  int n;  // layers incl. the output layer
-  MlpLayer l[PPO_MAX_LAYERS + 1];
-};
 struct ConvParams {
   int64_t w, b;  // torch-order weight [co][ci][k][k] and bias offsets
 };
@@ -235,20 +227,12 @@ __global__ __launch_bounds__(256) void pixel_env_step_kernel(PixelArgs p) {
 using namespace ppo;
 using namespace ppo::cnn;
 
-struct ppo_cnn_ctx {
+struct ppo_cnn_ctx : EncoderCtx {
   ppo_cnn_cfg cfg;
-  int device;
-  int prec;
-  float ent_log_share;  // ppo_*_loss_entropy_share (logged actor loss only)
   ConvParams conv[2][3];   // per net, per encoder layer
   int64_t logstd_off;
   Mlp mlp[2];              // actor mean MLP, critic MLP (input: 3136 features)
-  int64_t total, n_actor;
-  std::vector<int64_t> offsets;  // torch parameters() order, actor then critic
-  float *params;
   const uint64_t *rng_counter;
-  float *ws;
-  int64_t rows;
   // workspace views (per net z)
   float *wpack[2][3];                 // packed conv weights [co][(ky kx) ci]
   __bf16 *wdg[2][2];                  // bf16 W'^T of L2 / L3 for dgrad_lds_kernel (conv_lds.h)
@@ -264,54 +248,20 @@ struct ppo_cnn_ctx {
   int64_t cslab_stride[3];
   int cslab_splits_last[3];           // split counts of the last encoder backward
   float *ls_part, *loss_part;         // [kHeadSplits][A], [kHeadSplits][2]
-  int maxw;
-  Timing tim;
 };
 
 namespace {
 
-void add_mlp(Mlp &m, int in, const ppo_cnn_cfg &c, int out, int final_act, bool bias, int64_t &off,
-             std::vector<int64_t> &offs) {
-  m.n = c.n_hidden + 1;
-  for (int l = 0; l < m.n; ++l) {
-    MlpLayer &L = m.l[l];
-    L.in = in;
-    L.out = l < c.n_hidden ? c.hidden[l] : out;
-    L.act = l < c.n_hidden ? c.activation : final_act;
-    L.w = off;
-    offs.push_back(off);
-    off = align_up(off + static_cast<int64_t>(L.in) * L.out, kAlign);
-    if (bias) {
-      L.b = off;
-      offs.push_back(off);
-      off = align_up(off + L.out, kAlign);
-    } else {
-      L.b = -1;
-    }
-    in = L.out;
-  }
-}
-
 template <class G>
-void add_conv(ConvParams &cp, int64_t &off, std::vector<int64_t> &offs) {
-  cp.w = off;
-  offs.push_back(off);
-  off = align_up(off + static_cast<int64_t>(G::cout) * G::kdim, kAlign);
-  cp.b = off;
-  offs.push_back(off);
-  off = align_up(off + G::cout, kAlign);
+void add_conv(ConvParams &cp, ParamLayout &lay) {
+  cp.w = lay.add(static_cast<int64_t>(G::cout) * G::kdim);
+  cp.b = lay.add(G::cout);
 }
 
 template <class G>
 int64_t slab_floats() { return align_up(static_cast<int64_t>(G::cout) * G::kdim + G::cout, 4); }
 
-int check_rows(const ppo_cnn_ctx *x, int b) {
-  PPO_REQUIRE(x != nullptr, "ppo_cnn: null ctx");
-  PPO_REQUIRE(b >= 0 && b <= x->rows, "ppo_cnn: %d rows exceed the workspace (%lld)", b,
-              static_cast<long long>(x->rows));
-  PPO_REQUIRE(x->params != nullptr, "ppo_cnn: parameters not bound (ppo_cnn_bind_params)");
-  return 0;
-}
+int check_rows(const ppo_cnn_ctx *x, int b) { return ctx_check_rows(x, "ppo_cnn", b); }
 
 // ---- encoder launches ---------------------------------------------------------------------------
 template <class G, int MODE>
@@ -695,105 +645,27 @@ int encoder_backward(ppo_cnn_ctx *x, const uint8_t *frames, const int32_t *rows,
                                   : encoder_backward_t<float, false>(x, frames, rows, b, st);
 }
 
-// ---- MLP heads (gemm.h) ---------------------------------------------------------------------------
-// Forward of both MLPs (net z reads x->feat[z]); layers of equal shape share a launch.
-int mlp_forward(ppo_cnn_ctx *x, int b, hipStream_t st) {
-  const float *P = x->params;
-  for (int l = 0; l < x->mlp[0].n; ++l) {
-    GemmProblem p[2] = {};
-    for (int z = 0; z < 2; ++z) {
-      const MlpLayer &L = x->mlp[z].l[l];
-      p[z].a = l == 0 ? x->feat[z] : x->act[z][l - 1];
-      p[z].lda = L.in;
-      p[z].b = P + L.w;
-      p[z].ldb = L.in;
-      p[z].c = x->act[z][l];
-      p[z].ldc = L.out;
-      p[z].bias = L.b >= 0 ? P + L.b : nullptr;
-      p[z].m = b;
-      p[z].n = L.out;
-    }
-    const MlpLayer &LA = x->mlp[0].l[l], &LC = x->mlp[1].l[l];
-    const bool same = LA.in == LC.in && LA.out == LC.out && LA.act == LC.act;
-    for (int z = 0; z < (same ? 1 : 2); ++z) {
-      GemmBatch gb{};
-      gb.p[0] = p[z];
-      if (same) gb.p[1] = p[1];
-      gb.k = x->mlp[z].l[l].in;
-      gb.act = x->mlp[z].l[l].act;
-      gb.prec = x->prec;
-      if (int rc = gemm_rows_fwd_nk(gb, same ? 2 : 1, b, x->mlp[z].l[l].out, st))
-        return rc;
-    }
-  }
-  return 0;
-}
-
-// Backward of both MLPs from x->dz[z][0] (gradient at the output layer's pre-activation): weight
-// gradients into the MLP slabs, the input gradient times relu'(features) into x->dfeat[z].
-int mlp_backward(ppo_cnn_ctx *x, int b, int splits, hipStream_t st) {
-  const float *P = x->params;
-  float *cur[2] = {x->dz[0][0], x->dz[1][0]};
-  for (int l = x->mlp[0].n - 1; l >= 0; --l) {
-    GemmProblem pw[2] = {}, px[2] = {};
-    float *nxt[2] = {nullptr, nullptr};
-    for (int z = 0; z < 2; ++z) {
-      const MlpLayer &L = x->mlp[z].l[l];
-      pw[z].a = cur[z];
-      pw[z].lda = L.out;
-      pw[z].b = l == 0 ? x->feat[z] : x->act[z][l - 1];
-      pw[z].ldb = L.in;
-      pw[z].c = x->mlp_slabs + L.w;
-      pw[z].ldc = L.in;
-      pw[z].colsum = L.b >= 0 ? x->mlp_slabs + L.b : nullptr;
-      pw[z].m = L.out;
-      pw[z].n = L.in;
-      px[z].a = cur[z];
-      px[z].lda = L.out;
-      px[z].b = P + L.w;
-      px[z].ldb = L.in;
-      if (l > 0) {
-        nxt[z] = x->dz[z][cur[z] == x->dz[z][0] ? 1 : 0];
-        px[z].c = nxt[z];
-        px[z].aux = x->act[z][l - 1];
-      } else {
-        px[z].c = x->dfeat[z];
-        px[z].aux = x->feat[z];
-      }
-      px[z].ldc = L.in;
-      px[z].m = b;
-      px[z].n = L.in;
-    }
-    const MlpLayer &LA = x->mlp[0].l[l], &LC = x->mlp[1].l[l];
-    const bool same = LA.in == LC.in && LA.out == LC.out;
-    for (int z = 0; z < (same ? 1 : 2); ++z) {
-      GemmBatch gw{};
-      gw.p[0] = pw[z];
-      if (same) gw.p[1] = pw[1];
-      gw.k = b;
-      gw.splits = splits;
-      gw.slab_stride = x->total;
-      gw.prec = x->prec;
-      if (int rc = gemm_wgrad_partial(gw, same ? 2 : 1, x->mlp[z].l[l].out, x->mlp[z].l[l].in, st))
-        return rc;
-      GemmBatch gx{};
-      gx.p[0] = px[z];
-      if (same) gx.p[1] = px[1];
-      gx.k = x->mlp[z].l[l].out;
-      gx.act = l > 0 ? x->mlp[z].l[l - 1].act : PPO_ACT_RELU;  // the encoder's output ReLU
-      gx.prec = x->prec;
-      if (int rc = gemm_rows_dx(gx, same ? 2 : 1, b, x->mlp[z].l[l].in, st))
-        return rc;
-    }
-    cur[0] = nxt[0];
-    cur[1] = nxt[1];
-  }
-  return 0;
+// ---- MLP heads (mlp_ladder.h) ---------------------------------------------------------------------
+// Both MLPs as one ladder: net z reads x->feat[z]; backward from x->dz[z][0], the input gradient
+// times relu'(features) -- the encoder's output ReLU -- into x->dfeat[z].
+MlpLadder mlp_ladder(const ppo_cnn_ctx *x, int splits) {
+  MlpLadder q{};
+  q.prec = x->prec;
+  q.params = x->params;
+  q.np = 2;
+  for (int z = 0; z < 2; ++z)
+    q.p[z] = MlpProblem{&x->mlp[z], x->feat[z], nullptr, x->act[z], x->dz[z], x->dfeat[z]};
+  q.slabs = x->mlp_slabs;
+  q.splits = splits;
+  q.slab_stride = x->total;
+  q.ld_din = kFeatures;
+  q.in_act = PPO_ACT_RELU;
+  return q;
 }
 
 int forward_all(ppo_cnn_ctx *x, const uint8_t *frames, const int32_t *rows, int b, hipStream_t st) {
   if (int rc = encoder_forward(x, frames, rows, b, st)) return rc;
-  return mlp_forward(x, b, st);
+  return mlp_forward(mlp_ladder(x, 0), b, st);
 }
 
 }  // namespace
@@ -823,22 +695,20 @@ extern "C" int ppo_cnn_ctx_create(const ppo_cnn_cfg *cfg, int device, ppo_cnn_ct
   x->prec = PPO_PREC_F32;
   x->ent_log_share = 1.f;
   const int A = c.act_dim;
-  int64_t off = 0;
+  ParamLayout lay{&x->offsets};
   // actor: actor_logstd (the module's own parameter comes first in parameters()), encoder, MLP
-  x->logstd_off = off;
-  x->offsets.push_back(off);
-  off = align_up(off + A, kAlign);
-  add_conv<L1>(x->conv[0][0], off, x->offsets);
-  add_conv<L2>(x->conv[0][1], off, x->offsets);
-  add_conv<L3>(x->conv[0][2], off, x->offsets);
-  add_mlp(x->mlp[0], kFeatures, c, A, PPO_ACT_TANH, c.use_bias != 0, off, x->offsets);
-  x->n_actor = off;
+  x->logstd_off = lay.add(A);
+  add_conv<L1>(x->conv[0][0], lay);
+  add_conv<L2>(x->conv[0][1], lay);
+  add_conv<L3>(x->conv[0][2], lay);
+  add_mlp(x->mlp[0], kFeatures, c, A, PPO_ACT_TANH, c.use_bias != 0, lay);
+  x->n_actor = lay.total();
   // critic: encoder, MLP (the reference critic's layers always have biases, critic.py:20)
-  add_conv<L1>(x->conv[1][0], off, x->offsets);
-  add_conv<L2>(x->conv[1][1], off, x->offsets);
-  add_conv<L3>(x->conv[1][2], off, x->offsets);
-  add_mlp(x->mlp[1], kFeatures, c, 1, PPO_ACT_IDENTITY, true, off, x->offsets);
-  x->total = off;
+  add_conv<L1>(x->conv[1][0], lay);
+  add_conv<L2>(x->conv[1][1], lay);
+  add_conv<L3>(x->conv[1][2], lay);
+  add_mlp(x->mlp[1], kFeatures, c, 1, PPO_ACT_IDENTITY, true, lay);
+  x->total = lay.total();
   int maxw = std::max(A, 1);
   for (int l = 0; l < c.n_hidden; ++l) maxw = std::max(maxw, c.hidden[l]);
   x->maxw = maxw;
@@ -847,116 +717,60 @@ extern "C" int ppo_cnn_ctx_create(const ppo_cnn_cfg *cfg, int device, ppo_cnn_ct
   x->cslab_stride[0] = slab_floats<L1>();
   x->cslab_stride[1] = slab_floats<L2>();
   x->cslab_stride[2] = slab_floats<L3>();
-  int64_t need = 0;
-  auto take = [&](int64_t n) {
-    const int64_t at = need;
-    need = align_up(need + n, kWsAlign);
-    return at;
-  };
-  int64_t o_wdg[2][2], o_wfw[2][2], o_pack[2][3], o_a1[2], o_a2[2], o_feat[2], o_act[2][PPO_MAX_LAYERS + 1], o_dz[2][2],
-      o_dfeat[2], o_dz2[2], o_dz1[2], o_cslab[2][3];
+  Workspace ws(kWsAlign);
   const int64_t ksz[3] = {static_cast<int64_t>(L1::cout) * L1::kdim,
                           static_cast<int64_t>(L2::cout) * L2::kdim,
                           static_cast<int64_t>(L3::cout) * L3::kdim};
   for (int z = 0; z < 2; ++z) {
-    for (int l = 0; l < 3; ++l) o_pack[z][l] = take(ksz[l]);
-    o_wdg[z][0] = take(L2D::N * L2D::KD / 2);  // bf16
-    o_wdg[z][1] = take(L3D::N * L3D::KD / 2);
-    o_wfw[z][0] = take(L2F::CO * L2F::KD / 2);
-    o_wfw[z][1] = take(L3F::CO * L3F::KD / 2);
-    o_a1[z] = take(R * L1::P * L1::cout);  // f32-sized (bf16 uses half)
-    o_a2[z] = take(R * L2::P * L2::cout);
-    o_feat[z] = take(R * kFeatures);
-    for (int l = 0; l < x->mlp[z].n; ++l) o_act[z][l] = take(R * x->mlp[z].l[l].out);
-    o_dz[z][0] = take(R * maxw);
-    o_dz[z][1] = take(R * maxw);
-    o_dfeat[z] = take(R * kFeatures);
-    o_dz2[z] = take(R * L2::P * L2::cout);
-    o_dz1[z] = take(R * L1::P * L1::cout);
-    for (int l = 0; l < 3; ++l) o_cslab[z][l] = take(kConvMaxSplits * x->cslab_stride[l]);
+    for (int l = 0; l < 3; ++l) ws.take_n(&x->wpack[z][l], ksz[l]);
+    ws.take_n(&x->wdg[z][0], L2D::N * L2D::KD);
+    ws.take_n(&x->wdg[z][1], L3D::N * L3D::KD);
+    ws.take_n(&x->wfw[z][0], L2F::CO * L2F::KD);
+    ws.take_n(&x->wfw[z][1], L3F::CO * L3F::KD);
+    ws.take(&x->a1[z], R * L1::P * L1::cout * 4);  // bytes: f32-sized (bf16 uses half)
+    ws.take(&x->a2[z], R * L2::P * L2::cout * 4);
+    ws.take_n(&x->feat[z], R * kFeatures);
+    for (int l = 0; l < x->mlp[z].n; ++l) ws.take_n(&x->act[z][l], R * x->mlp[z].l[l].out);
+    ws.take_n(&x->dz[z][0], R * maxw);
+    ws.take_n(&x->dz[z][1], R * maxw);
+    ws.take_n(&x->dfeat[z], R * kFeatures);
+    ws.take_n(&x->dz2[z], R * L2::P * L2::cout);
+    ws.take_n(&x->dz1[z], R * L1::P * L1::cout);
+    for (int l = 0; l < 3; ++l) ws.take_n(&x->cslab[z][l], kConvMaxSplits * x->cslab_stride[l]);
   }
-  const int64_t o_mslab = take(kMlpSplits * x->total);
-  const int64_t o_ls = take(static_cast<int64_t>(kHeadSplits) * A);
-  const int64_t o_loss = take(static_cast<int64_t>(kHeadSplits) * 2);
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc(&x->ws, sizeof(float) * std::max<int64_t>(need, 1));
-  if (e == hipSuccess) e = hipMemset(x->ws, 0, sizeof(float) * std::max<int64_t>(need, 1));
-  if (e != hipSuccess) {
-    set_error("ppo_cnn_ctx_create: allocating %lld floats of workspace failed: %s",
-              static_cast<long long>(need), hipGetErrorString(e));
-    if (x->ws) (void)hipFree(x->ws);
-    delete x;
-    return PPO_EHIP;
+  ws.take_n(&x->mlp_slabs, kMlpSplits * x->total);
+  ws.take_n(&x->ls_part, static_cast<int64_t>(kHeadSplits) * A);
+  ws.take_n(&x->loss_part, static_cast<int64_t>(kHeadSplits) * 2);
+  if (int rc = workspace_alloc(ws, "ppo_cnn_ctx_create", device, true, &x->ws)) {
+    ppo_cnn_ctx_destroy(x);
+    return rc;
   }
-  float *w = x->ws;
-  for (int z = 0; z < 2; ++z) {
-    for (int l = 0; l < 3; ++l) {
-      x->wpack[z][l] = w + o_pack[z][l];
-      if (l < 2) x->wdg[z][l] = reinterpret_cast<__bf16 *>(w + o_wdg[z][l]);
-      if (l < 2) x->wfw[z][l] = reinterpret_cast<__bf16 *>(w + o_wfw[z][l]);
-      x->cslab[z][l] = w + o_cslab[z][l];
-    }
-    x->a1[z] = w + o_a1[z];
-    x->a2[z] = w + o_a2[z];
-    x->feat[z] = w + o_feat[z];
-    for (int l = 0; l < x->mlp[z].n; ++l) x->act[z][l] = w + o_act[z][l];
-    x->dz[z][0] = w + o_dz[z][0];
-    x->dz[z][1] = w + o_dz[z][1];
-    x->dfeat[z] = w + o_dfeat[z];
-    x->dz2[z] = w + o_dz2[z];
-    x->dz1[z] = w + o_dz1[z];
-  }
-  x->mlp_slabs = w + o_mslab;
-  x->ls_part = w + o_ls;
-  x->loss_part = w + o_loss;
   *out = x;
   return 0;
 }
 
 extern "C" int ppo_cnn_ctx_destroy(ppo_cnn_ctx *x) {
   if (!x) return 0;
-  (void)timing_enable(x->tim, 0, 0);
-  for (int i = 0; i < 2 * x->tim.capacity; ++i) (void)hipEventDestroy(x->tim.ev[i]);
-  delete[] x->tim.ev;
-  delete[] x->tim.cls;
-  delete[] x->tim.kname;
-  delete[] x->tim.flops;
-  delete[] x->tim.bytes;
-  if (x->ws) (void)hipFree(x->ws);
+  ctx_release(x);
   delete x;
   return 0;
 }
 
 extern "C" int ppo_cnn_param_layout(const ppo_cnn_ctx *x, int64_t *offsets, int max_tensors,
                                     int64_t *total, int64_t *n_actor) {
-  PPO_REQUIRE(x != nullptr, "ppo_cnn_param_layout: null ctx");
-  const int n = static_cast<int>(x->offsets.size());
-  if (offsets)
-    for (int i = 0; i < std::min(n, max_tensors); ++i) offsets[i] = x->offsets[i];
-  if (total) *total = x->total;
-  if (n_actor) *n_actor = x->n_actor;
-  return n;
+  return ctx_param_layout(x, "ppo_cnn_param_layout", offsets, max_tensors, total, n_actor);
 }
 
 extern "C" int ppo_cnn_bind_params(ppo_cnn_ctx *x, float *params_d) {
-  PPO_REQUIRE(x != nullptr && params_d != nullptr, "ppo_cnn_bind_params: null argument");
-  PPO_REQUIRE(reinterpret_cast<uintptr_t>(params_d) % 64 == 0,
-              "ppo_cnn_bind_params: parameter buffer must be 64-B aligned");
-  x->params = params_d;
-  return 0;
+  return ctx_bind_params(x, "ppo_cnn_bind_params", params_d);
 }
 
 extern "C" int ppo_cnn_loss_entropy_share(ppo_cnn_ctx *x, float share) {
-  PPO_REQUIRE(x != nullptr, "ppo_cnn_loss_entropy_share: null ctx");
-  x->ent_log_share = share;
-  return 0;
+  return ctx_loss_entropy_share(x, "ppo_cnn_loss_entropy_share", share);
 }
 
 extern "C" int ppo_cnn_set_precision(ppo_cnn_ctx *x, int prec) {
-  PPO_REQUIRE(x != nullptr, "ppo_cnn_set_precision: null ctx");
-  PPO_REQUIRE(prec == PPO_PREC_F32 || prec == PPO_PREC_BF16, "ppo_cnn_set_precision: %d", prec);
-  x->prec = prec;
-  return 0;
+  return ctx_set_precision(x, "ppo_cnn_set_precision", prec);
 }
 
 extern "C" int ppo_cnn_set_rng_counter(ppo_cnn_ctx *x, const uint64_t *counter_d) {
@@ -1066,7 +880,7 @@ extern "C" int ppo_cnn_minibatch_grad(ppo_cnn_ctx *x, const uint8_t *frames_d,
            dim3(head_splits), dim3(256), 0, st, h);
   PPO_LAUNCHED();
   const int mlp_splits = std::min(kMlpSplits, std::max(1, b / 512));
-  if (int rc = mlp_backward(x, b, mlp_splits, st)) return rc;
+  if (int rc = mlp_backward(mlp_ladder(x, mlp_splits), b, st)) return rc;
   if (int rc = encoder_backward(x, frames_d, rows_d, b, st)) return rc;
 
   // slabs -> flat gradient in ascending tensor order, each in a fixed split order
@@ -1099,15 +913,14 @@ extern "C" int ppo_cnn_minibatch_grad(ppo_cnn_ctx *x, const uint8_t *frames_d,
 }
 
 extern "C" int ppo_cnn_timing(ppo_cnn_ctx *x, int enable, int capacity) {
-  PPO_REQUIRE(x != nullptr, "ppo_cnn_timing: null ctx");
-  return timing_enable(x->tim, enable, capacity);
+  return ctx_timing(x, "ppo_cnn_timing", enable, capacity);
 }
 
 extern "C" int ppo_cnn_timing_kernel(ppo_cnn_ctx *x, int index, const char **name, int *kclass,
                                      double *total_ms, int64_t *launches, double *flops,
                                      double *bytes) {
-  PPO_REQUIRE(x != nullptr, "ppo_cnn_timing_kernel: null ctx");
-  return timing_read_kernel(x->tim, index, name, kclass, total_ms, launches, flops, bytes);
+  return ctx_timing_kernel(x, "ppo_cnn_timing_kernel", index, name, kclass, total_ms, launches,
+                           flops, bytes);
 }
 
 extern "C" int ppo_synthetic_pixel_step(uint32_t seed, int t, const float *action_d, int n, int h,

@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "ppo_engine.h"
+#include "workspace.h"
 
 namespace ppo {
 
@@ -38,7 +39,23 @@ void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int ceil_div(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) / b); }
-inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+// Allocates the arena a Workspace planned and binds its buffers; errors are reported in the
+// caller's name `who`.  device >= 0: made current first.  zero: the whole arena is cleared.
+inline int workspace_alloc(const Workspace &ws, const char *who, int device, bool zero,
+                           void **arena) {
+  const size_t bytes = static_cast<size_t>(ws.bytes() > 0 ? ws.bytes() : 1);
+  hipError_t e = device >= 0 ? hipSetDevice(device) : hipSuccess;
+  if (e == hipSuccess) e = hipMalloc(arena, bytes);
+  if (e == hipSuccess && zero) e = hipMemset(*arena, 0, bytes);
+  if (e != hipSuccess) {
+    set_error("%s: allocating %zu bytes of workspace failed: %s", who, bytes,
+              hipGetErrorString(e));
+    return PPO_EHIP;
+  }
+  ws.bind(*arena);
+  return 0;
+}
 
 // An integer experiment knob from the environment (callers read it once, into a static).
 inline int env_knob(const char *name, int dflt) {

@@ -22,9 +22,6 @@
 
 namespace ppo {
 
-constexpr int64_t kParamAlign = 16;  // floats: every flat tensor starts 64-B aligned
-constexpr int64_t kWsAlign = 64;     // floats: workspace buffers start 256-B aligned
-
 static const int g_fused_enabled = env_knob("PPO_FUSED", 1);
 // PPO_FUSED_DIRECT=0: the 8-wave fused update reads the gathered xb / srow copies (written by the
 // prep kernel or the previous step tail) instead of the staged records through the row indices
@@ -281,22 +278,18 @@ extern "C" int ppo_ctx_create(const ppo_net_cfg *cfg, int device, ppo_ctx **out)
   ctx->device = device;
   ctx->ent_log_share = 1.f;
   const int din = cfg->obs_dim * cfg->window;
-  int64_t off = 0;
-  int64_t ws_floats = 0;
+  ParamLayout lay;
   const int64_t R = cfg->max_rows;
+  // layered arena: 256 spare bytes at the end
+  Workspace ws(kWsAlign, 0, 256);
   for (int z = 0; z < 2; ++z) {
     NetDesc &nd = ctx->net[z];
-    nd.begin = off;
+    nd.begin = lay.total();
     const int nh = z == 0 ? cfg->n_actor_hidden : cfg->n_critic_hidden;
     const int32_t *hid = z == 0 ? cfg->actor_hidden : cfg->critic_hidden;
     const bool bias = z == 0 ? cfg->actor_use_bias != 0 : true;
     nd.n_hidden = nh;
-    if (z == 0) {
-      nd.logstd_off = off;
-      off = align_up(off + cfg->act_dim, kParamAlign);
-    } else {
-      nd.logstd_off = -1;
-    }
+    nd.logstd_off = z == 0 ? lay.add(cfg->act_dim) : -1;
     int width = din;
     for (int l = 0; l <= nh; ++l) {
       const int o = (l < nh) ? hid[l] : (z == 0 ? cfg->act_dim : 1);
@@ -308,20 +301,17 @@ extern "C" int ppo_ctx_create(const ppo_net_cfg *cfg, int device, ppo_ctx **out)
       LayerDesc &L = nd.layer[l];
       L.in = width;
       L.out = o;
-      L.w_off = off;
-      off = align_up(off + static_cast<int64_t>(o) * width, kParamAlign);
-      L.b_off = bias ? off : -1;
-      if (bias) off = align_up(off + o, kParamAlign);
-      if (l < nh) ws_floats += align_up(R * o, kWsAlign);
+      L.w_off = lay.add(static_cast<int64_t>(o) * width);
+      L.b_off = bias ? lay.add(o) : -1;
+      if (l < nh) ws.take_n(&nd.h[l], R * o);  // hidden outputs (max_rows, width)
       width = o;
     }
-    ws_floats += align_up(R * nd.layer[nh].in, kWsAlign);   // g = dH_L (last hidden width)
-    ws_floats += align_up(R * nd.layer[nh].out, kWsAlign);  // dz
-    nd.count = off - nd.begin;
+    ws.take_n(&nd.g, R * nd.layer[nh].in);    // g = dH_L (last hidden width)
+    ws.take_n(&nd.dz, R * nd.layer[nh].out);  // dz
+    nd.count = lay.total() - nd.begin;
   }
+  const int64_t off = lay.total();
   ctx->total_params = off;
-  ws_floats += align_up(static_cast<int64_t>(kSlabSplits) * off, kWsAlign);
-  ws_floats += align_up(static_cast<int64_t>(kHeadSplits) * (cfg->act_dim + 2), kWsAlign);
   {
     const int A = cfg->act_dim;
     const int da = ctx->net[0].layer[ctx->net[0].n_hidden].in;
@@ -331,107 +321,56 @@ extern "C" int ppo_ctx_create(const ppo_net_cfg *cfg, int device, ppo_ctx **out)
     ctx->hw_off_bc = ctx->hw_off_wc + static_cast<int>(align_up(dc, 4));
     ctx->hw_stride = ctx->hw_off_bc + 4;
   }
-  ws_floats += align_up(static_cast<int64_t>(kHeadSplits) * ctx->hw_stride, kWsAlign);
-  const int ldx = static_cast<int>(align_up(din, 4));
-  ws_floats += align_up(R * ldx, kWsAlign);
-  void *arena = nullptr;
-  hipError_t e = hipMalloc(&arena, ws_floats * sizeof(float) + 256);
-  if (e != hipSuccess) {
-    delete ctx;
-    set_error("ppo_ctx_create: hipMalloc(%zu bytes) failed: %s", ws_floats * sizeof(float),
-              hipGetErrorString(e));
-    return PPO_EHIP;
+  ctx->ldx = static_cast<int>(align_up(din, 4));
+  ws.take_n(&ctx->slabs, static_cast<int64_t>(kSlabSplits) * off);
+  ws.take_n(&ctx->head_part, static_cast<int64_t>(kHeadSplits) * (cfg->act_dim + 2));
+  ws.take_n(&ctx->head_w_part, static_cast<int64_t>(kHeadSplits) * ctx->hw_stride);
+  ws.take_n(&ctx->xg, R * ctx->ldx);  // gathered minibatch states (max_rows, ldx)
+  if (int rc = workspace_alloc(ws, "ppo_ctx_create", -1, false, &ctx->arena)) {
+    ppo_ctx_destroy(ctx);
+    return rc;
   }
-  ctx->arena = arena;
-  float *p = static_cast<float *>(arena);
-  for (int z = 0; z < 2; ++z) {
-    NetDesc &nd = ctx->net[z];
-    for (int l = 0; l < nd.n_hidden; ++l) {
-      nd.h[l] = p;
-      p += align_up(R * nd.layer[l].out, kWsAlign);
-    }
-    nd.g = p;
-    p += align_up(R * nd.layer[nd.n_hidden].in, kWsAlign);
-    nd.dz = p;
-    p += align_up(R * nd.layer[nd.n_hidden].out, kWsAlign);
-  }
-  ctx->slabs = p;
-  p += align_up(static_cast<int64_t>(kSlabSplits) * off, kWsAlign);
-  ctx->head_part = p;
-  p += align_up(static_cast<int64_t>(kHeadSplits) * (cfg->act_dim + 2), kWsAlign);
-  ctx->head_w_part = p;
-  p += align_up(static_cast<int64_t>(kHeadSplits) * ctx->hw_stride, kWsAlign);
-  ctx->xg = p;
-  ctx->ldx = ldx;
-  p += align_up(R * ldx, kWsAlign);
-  if (static_cast<int64_t>(p - static_cast<float *>(arena)) != ws_floats) {
-    (void)hipFree(arena);
-    delete ctx;
-    set_error("ppo_ctx_create: internal workspace carve-out mismatch");
-    return PPO_EHIP;
-  }
-  ctx->params = nullptr;
   // fused bf16 update: both nets 2 hidden layers of one compiled width, W*O <= 32, A <= 8
-  {
-    const NetDesc &na = ctx->net[0], &nc = ctx->net[1];
-    const int H = na.layer[0].out;
-    ctx->fused_ok = na.n_hidden == 2 && nc.n_hidden == 2 && fused_width_ok(H) &&
-                    na.layer[1].out == H && nc.layer[0].out == H && nc.layer[1].out == H &&
-                    din <= kFusedKX && cfg->act_dim <= kFusedMaxAct;
-    ctx->fused_hidden = H;
-    if (ctx->fused_ok) {
-      const int64_t wimg = align_up(static_cast<int64_t>(H) * (kFusedKX + 2 * H), 128);
-      const int64_t cimg = align_up(fused_const_bytes(H), 256);
-      const int64_t bytes = 2 * wimg * 2 + 2 * cimg + align_up(R * kFusedKX * 2, 256) +
-                            align_up(R * kFusedSP * 4, 256) +
-                            static_cast<int64_t>(kFusedMaxWG) * off * 4 + kFusedMaxWG * 2 * 4 + 1024;
-      void *fa = nullptr;
-      e = hipMalloc(&fa, bytes);
-      if (e != hipSuccess) {
-        (void)hipFree(arena);
-        delete ctx;
-        set_error("ppo_ctx_create: hipMalloc(%lld bytes) for the fused workspace failed: %s",
-                  static_cast<long long>(bytes), hipGetErrorString(e));
-        return PPO_EHIP;
-      }
-      ctx->farena = fa;
-      char *c = static_cast<char *>(fa);
-      for (int z = 0; z < 2; ++z) {
-        __bf16 *wb = reinterpret_cast<__bf16 *>(c);
-        ctx->fw[z][0] = wb;
-        ctx->fw[z][1] = wb + static_cast<int64_t>(H) * kFusedKX;
-        ctx->fw[z][2] = wb + static_cast<int64_t>(H) * (kFusedKX + H);
-        c += wimg * 2;
-      }
-      {  // the constants images, their pads written here once (the writers store parameters only)
-        char *pads = new (std::nothrow) char[fused_const_bytes(H)];
-        e = pads ? hipSuccess : hipErrorOutOfMemory;
-        for (int z = 0; z < 2 && e == hipSuccess; ++z) {
-          ctx->fconst[z] = c;
-          c += cimg;
-          fused_const_pads(H, pads);
-          e = hipMemcpy(ctx->fconst[z], pads, fused_const_bytes(H), hipMemcpyHostToDevice);
-        }
-        delete[] pads;
-        if (e != hipSuccess) {
-          (void)hipFree(fa);
-          (void)hipFree(arena);
-          delete ctx;
-          set_error("ppo_ctx_create: writing the fused constants images failed: %s",
-                    hipGetErrorString(e));
-          return PPO_EHIP;
-        }
-      }
-      ctx->fxb = reinterpret_cast<__bf16 *>(c);
-      c += align_up(R * kFusedKX * 2, 256);
-      ctx->fsrow = reinterpret_cast<float *>(c);
-      c += align_up(R * kFusedSP * 4, 256);
-      ctx->fslabs = reinterpret_cast<float *>(c);
-      c += static_cast<int64_t>(kFusedMaxWG) * off * 4;
-      ctx->floss = reinterpret_cast<float *>(c);
-      c += kFusedMaxWG * 2 * 4;
-      ctx->fdirect = g_fused_direct != 0;
+  const NetDesc &na = ctx->net[0], &nc = ctx->net[1];
+  const int H = na.layer[0].out;
+  ctx->fused_ok = na.n_hidden == 2 && nc.n_hidden == 2 && fused_width_ok(H) &&
+                  na.layer[1].out == H && nc.layer[0].out == H && nc.layer[1].out == H &&
+                  din <= kFusedKX && cfg->act_dim <= kFusedMaxAct;
+  ctx->fused_hidden = H;
+  if (ctx->fused_ok) {
+    // fused arena: W images rounded to 128 elements, 1 KB at the end
+    Workspace fws(kWsAlign, 0, 1024);
+    for (int z = 0; z < 2; ++z)  // per net one block: W0 image (H, 32), W1 (H, H), W1^T (H, H)
+      fws.take_n(&ctx->fw[z][0], align_up(static_cast<int64_t>(H) * (kFusedKX + 2 * H), 128));
+    for (int z = 0; z < 2; ++z) fws.take(&ctx->fconst[z], fused_const_bytes(H));
+    fws.take_n(&ctx->fxb, R * kFusedKX);    // (max_rows, 32) staged bf16 states
+    fws.take_n(&ctx->fsrow, R * kFusedSP);  // (max_rows, 16) staged row scalars
+    fws.take_n(&ctx->fslabs, static_cast<int64_t>(kFusedMaxWG) * off);
+    fws.take_n(&ctx->floss, kFusedMaxWG * 2);
+    if (int rc = workspace_alloc(fws, "ppo_ctx_create (fused workspace)", -1, false,
+                                 &ctx->farena)) {
+      ppo_ctx_destroy(ctx);
+      return rc;
     }
+    for (int z = 0; z < 2; ++z) {
+      ctx->fw[z][1] = ctx->fw[z][0] + static_cast<int64_t>(H) * kFusedKX;
+      ctx->fw[z][2] = ctx->fw[z][0] + static_cast<int64_t>(H) * (kFusedKX + H);
+    }
+    // the constants images, their pads written here once (the writers store parameters only)
+    char *pads = new (std::nothrow) char[fused_const_bytes(H)];
+    hipError_t e = pads ? hipSuccess : hipErrorOutOfMemory;
+    for (int z = 0; z < 2 && e == hipSuccess; ++z) {
+      fused_const_pads(H, pads);
+      e = hipMemcpy(ctx->fconst[z], pads, fused_const_bytes(H), hipMemcpyHostToDevice);
+    }
+    delete[] pads;
+    if (e != hipSuccess) {
+      ppo_ctx_destroy(ctx);
+      set_error("ppo_ctx_create: writing the fused constants images failed: %s",
+                hipGetErrorString(e));
+      return PPO_EHIP;
+    }
+    ctx->fdirect = g_fused_direct != 0;
   }
   *out = ctx;
   return 0;
@@ -441,12 +380,7 @@ extern "C" int ppo_ctx_destroy(ppo_ctx *ctx) {
   if (!ctx) return 0;
   (void)hipSetDevice(ctx->device);
   if (g_free_tim == &ctx->tim) g_free_tim = nullptr;
-  for (int i = 0; i < 2 * ctx->tim.capacity; ++i) (void)hipEventDestroy(ctx->tim.ev[i]);
-  delete[] ctx->tim.ev;
-  delete[] ctx->tim.cls;
-  delete[] ctx->tim.kname;
-  delete[] ctx->tim.flops;
-  delete[] ctx->tim.bytes;
+  timing_release(ctx->tim);
   if (ctx->arena) (void)hipFree(ctx->arena);
   if (ctx->farena) (void)hipFree(ctx->farena);
   if (ctx->fstamps) (void)hipFree(ctx->fstamps);

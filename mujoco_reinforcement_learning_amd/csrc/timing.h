@@ -70,6 +70,8 @@ inline bool tim_active() { return g_tim != nullptr; }
 // implemented in timing.hip with the rest of this header's state:
 // enable (re)allocates `capacity` event pairs and clears the totals; read folds pending records.
 int timing_enable(Timing &t, int enable, int capacity);
+// destroys the events and frees the record arrays (a context's destroy; enable's regrowth)
+void timing_release(Timing &t);
 int timing_read_class(Timing &t, int kclass, double *total_ms, int64_t *launches, double *flops,
                       double *bytes);
 int timing_read_kernel(Timing &t, int index, const char **name, int *kclass, double *total_ms,

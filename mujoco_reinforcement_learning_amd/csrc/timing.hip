@@ -36,14 +36,18 @@ const char *intern_name(const char *fmt, ...) {
   return names.back().c_str();
 }
 
+void timing_release(Timing &t) {
+  for (int i = 0; i < 2 * t.capacity; ++i) (void)hipEventDestroy(t.ev[i]);
+  delete[] t.ev;
+  delete[] t.cls;
+  delete[] t.kname;
+  delete[] t.flops;
+  delete[] t.bytes;
+}
+
 int timing_enable(Timing &t, int enable, int capacity) {
   if (enable && capacity > t.capacity) {
-    for (int i = 0; i < 2 * t.capacity; ++i) (void)hipEventDestroy(t.ev[i]);
-    delete[] t.ev;
-    delete[] t.cls;
-    delete[] t.kname;
-    delete[] t.flops;
-    delete[] t.bytes;
+    timing_release(t);
     t.ev = new hipEvent_t[2 * capacity];
     t.cls = new int[capacity];
     t.kname = new const char *[capacity];

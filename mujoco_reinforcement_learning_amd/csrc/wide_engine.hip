@@ -81,34 +81,25 @@ int wide_alloc(ppo_ctx *ctx) {
   const int din = ctx->cfg.obs_dim * ctx->cfg.window;
   w->ldx = static_cast<int>(align_up(din, 128));  // whole 8-k-step groups for the fused rollout
   const int blocks = static_cast<int>(R / kWideLossRows);
-  // carve-out in bytes; every buffer 256-B aligned, 1 KB of slack after each (tile reads past a
-  // row end stay inside the allocation)
-  int64_t bytes = 0;
-  auto take = [&](int64_t b) {
-    const int64_t o = bytes;
-    bytes += align_up(b, 256) + 1024;
-    return o;
-  };
-  struct Off {
-    int64_t h[PPO_MAX_LAYERS], dh[PPO_MAX_LAYERS], w[PPO_MAX_LAYERS + 1], wt[PPO_MAX_LAYERS + 1],
-        cs[PPO_MAX_LAYERS];
-    int64_t dz, z;
-  } off[2];
-  const int64_t ox = take(R * w->ldx * 2);
-  int64_t img0 = -1, img_bytes = 0;
+  // every buffer 256-B aligned, 1 KB of slack after each (tile reads past a row end stay inside
+  // the allocation)
+  Workspace ws(kWsAlign, 1024);
+  ws.take(&w->x, R * w->ldx * 2);
   for (int z = 0; z < 2; ++z) {
     const NetDesc &nd = ctx->net[z];
     WideNetWork &wn = w->net[z];
     for (int l = 0; l < nd.n_hidden; ++l) {
       wn.ldh[l] = static_cast<int>(align_up(nd.layer[l].out, 64));
-      off[z].h[l] = take(R * wn.ldh[l] * 2);
-      off[z].dh[l] = take(R * wn.ldh[l] * 2);
-      off[z].cs[l] = take((R / 64) * nd.layer[l].out * 4);
+      ws.take(&wn.h[l], R * wn.ldh[l] * 2);
+      ws.take(&wn.dh[l], R * wn.ldh[l] * 2);
+      ws.take(&wn.colsum[l], (R / 64) * nd.layer[l].out * 4);
     }
-    off[z].dz = take(R * 64 * 2);
-    off[z].z = take(R * 32 * 4);
+    ws.take(&wn.dz, R * 64 * 2);
+    ws.take(&wn.z, R * 32 * 4);
   }
-  // weight images last and contiguous, so the pack kernel zero-fills them as one range
+  // weight images last, packed (no slack but after the last one) and contiguous, so the pack
+  // kernel zero-fills them as one range of img_elems from net[0].w[0]
+  int64_t img_bytes = 0;
   for (int z = 0; z < 2; ++z) {
     const NetDesc &nd = ctx->net[z];
     WideNetWork &wn = w->net[z];
@@ -118,15 +109,12 @@ int wide_alloc(ppo_ctx *ctx) {
       wn.ldwt[l] = static_cast<int>(align_up(L.out, 64));
       const int64_t a = align_up(align_up(L.out, 128) * wn.ldw[l] * 2, 256);
       const int64_t b = align_up(align_up(L.in, 128) * wn.ldwt[l] * 2, 256);
-      off[z].w[l] = bytes;
-      bytes += a;
-      off[z].wt[l] = bytes;
-      bytes += b;
-      if (img0 < 0) img0 = off[z].w[l];
-      img_bytes = bytes - img0;
+      ws.take(&wn.w[l], a, 0);
+      ws.take(&wn.wt[l], b, z == 1 && l == nd.n_hidden ? 1024 : 0);
+      img_bytes += a + b;
     }
   }
-  bytes += 1024;
+  w->img_elems = img_bytes / 2;
   // fused rollout: every hidden width a multiple of 128 and at most kFMaxW, the input row too,
   // the actor head at most 32 wide
   bool fr = w->ldx <= kFMaxW && ctx->cfg.act_dim <= 32;
@@ -134,8 +122,7 @@ int wide_alloc(ppo_ctx *ctx) {
     for (int l = 0; l < ctx->net[z].n_hidden; ++l)
       fr = fr && ctx->net[z].layer[l].out % 128 == 0 && ctx->net[z].layer[l].out <= kFMaxW;
   w->fused_rollout = fr && wide_fused_rollout_enabled();
-  int64_t off_wf[2][PPO_MAX_LAYERS + 1] = {};
-  if (w->fused_rollout)
+  if (w->fused_rollout)  // (wf stays null otherwise)
     for (int z = 0; z < 2; ++z) {
       const NetDesc &nd = ctx->net[z];
       WideNetWork &wn = w->net[z];
@@ -143,50 +130,17 @@ int wide_alloc(ppo_ctx *ctx) {
         const LayerDesc &L = nd.layer[l];
         wn.wf_tiles[l] = static_cast<int>(align_up(L.out, 32) / 32);
         wn.wf_ks[l] = static_cast<int>(align_up(L.in, 128) / 16);
-        off_wf[z][l] = take(static_cast<int64_t>(wn.wf_tiles[l]) * wn.wf_ks[l] * 512 * 2);
+        ws.take(&wn.wf[l], static_cast<int64_t>(wn.wf_tiles[l]) * wn.wf_ks[l] * 512 * 2);
       }
     }
-  const int64_t opart = take(static_cast<int64_t>(blocks) * kWidePart * 4);
-  const int64_t oloss = take(static_cast<int64_t>(blocks) * 2 * 4);
-  void *arena = nullptr;
-  hipError_t e = hipMalloc(&arena, bytes);
-  if (e != hipSuccess) {
-    delete w;
-    set_error("wide_alloc: hipMalloc(%lld bytes) failed: %s", static_cast<long long>(bytes),
-              hipGetErrorString(e));
-    return PPO_EHIP;
-  }
-  e = hipMemset(arena, 0, bytes);  // pad rows / columns of every operand stay zero
-  if (e != hipSuccess) {
-    (void)hipFree(arena);
-    delete w;
-    set_error("wide_alloc: hipMemset failed: %s", hipGetErrorString(e));
-    return PPO_EHIP;
-  }
-  char *base = static_cast<char *>(arena);
-  w->arena = arena;
-  w->x = reinterpret_cast<__bf16 *>(base + ox);
-  for (int z = 0; z < 2; ++z) {
-    const NetDesc &nd = ctx->net[z];
-    WideNetWork &wn = w->net[z];
-    for (int l = 0; l < nd.n_hidden; ++l) {
-      wn.h[l] = reinterpret_cast<__bf16 *>(base + off[z].h[l]);
-      wn.dh[l] = reinterpret_cast<__bf16 *>(base + off[z].dh[l]);
-      wn.colsum[l] = reinterpret_cast<float *>(base + off[z].cs[l]);
-    }
-    for (int l = 0; l <= nd.n_hidden; ++l) {
-      wn.w[l] = reinterpret_cast<__bf16 *>(base + off[z].w[l]);
-      wn.wt[l] = reinterpret_cast<__bf16 *>(base + off[z].wt[l]);
-    }
-    wn.dz = reinterpret_cast<__bf16 *>(base + off[z].dz);
-    wn.z = reinterpret_cast<float *>(base + off[z].z);
-    for (int l = 0; l <= nd.n_hidden; ++l)
-      wn.wf[l] = w->fused_rollout ? reinterpret_cast<__bf16 *>(base + off_wf[z][l]) : nullptr;
-  }
-  w->part = reinterpret_cast<float *>(base + opart);
-  w->loss_part = reinterpret_cast<float *>(base + oloss);
-  w->img_elems = img_bytes / 2;
+  ws.take(&w->part, static_cast<int64_t>(blocks) * kWidePart * 4);
+  ws.take(&w->loss_part, static_cast<int64_t>(blocks) * 2 * 4);
   ctx->wide = w;
+  // cleared whole: pad rows / columns of every operand stay zero
+  if (int rc = workspace_alloc(ws, "wide_alloc", -1, true, &w->arena)) {
+    wide_free(ctx);
+    return rc;
+  }
   return 0;
 }
 
