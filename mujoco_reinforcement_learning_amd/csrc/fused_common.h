@@ -240,44 +240,65 @@ __device__ __forceinline__ const __bf16 *w_frag_base(const __bf16 *img, int w, i
   return img + (static_cast<int64_t>(w) * 64 + lane) * 8;
 }
 
-template <int H>
+// KRES (resident k-steps): the pass's first KRES k-steps take the wave's A fragment from a
+// wave-private LDS copy of the image's head (`res`: this lane's 16 B of k-step 0, k-step s
+// 1 KB * NW further -- the image's own fragment-major order, so the copy is one straight run) and
+// only k-steps KRES.. run through the ring, which wring_prime then primes from k-step KRES.  The
+// MFMA order over k is the same for every KRES: bitwise the same accumulators.
+template <int H, int KRES = 0>
 __device__ __forceinline__ void wring_prime(const __bf16 *wfrag, bf16x8 (&ring)[PD + 1]) {
 #pragma unroll
-  for (int s = 0; s < PD; ++s) ring[s] = *reinterpret_cast<const bf16x8 *>(wfrag + static_cast<int64_t>(16 * H) * s);
+  for (int s = 0; s < PD; ++s)
+    ring[s] = *reinterpret_cast<const bf16x8 *>(wfrag + static_cast<int64_t>(16 * H) * (KRES + s));
 }
-template <int H, int NTILE>
+// SWAP: the product transposed (A = the image's row fragment, B = the weight fragment; the two
+// register formats are the same): acc[t] lane (r, h) register e = the same dot product, for
+// weight row 32w + r and image row 32t + reg_feature(e, h).
+template <int H, int NTILE, int KRES = 0, bool SWAP = false>
 __device__ __forceinline__ void mlp_pass(const __bf16 *wfrag, const char *img, int r, int h,
-                                         bf16x8 (&ring)[PD + 1], f32x16 (&acc)[NTILE]) {
+                                         bf16x8 (&ring)[PD + 1], f32x16 (&acc)[NTILE],
+                                         const char *res = nullptr) {
   constexpr int KS = H / 16;
-  static_assert(KS % (PD + 1) == 0, "ring period must divide the k-steps");
+  // the streamed k-steps end with a peeled tail of TL >= PD steps (4 when the ring period divides
+  // them, as with KRES = 0), so the rolled periods before it never prefetch past the image
+  constexpr int TL0 = (KS - KRES - 1) % (PD + 1) + 1, TL = TL0 < PD ? TL0 + PD + 1 : TL0;
+  static_assert(KRES >= 0 && KS - KRES >= TL, "too few streamed k-steps for the ring");
   const int swz = ((r & 3) << 2) | ((r >> 2) & 3);
   const char *rowp = img + r * (2 * H);
-  // rolled over all ring periods but the last (one load per k-step: the vmcnt waits of the rolled
+  const auto step = [&](bf16x8 af, int s) {
+    const char *p = rowp + 16 * ((2 * s + h) ^ swz);
+#pragma unroll
+    for (int t = 0; t < NTILE; ++t) {
+      const bf16x8 bv = lds_b128(p + t * 32 * (2 * H));
+      acc[t] = SWAP ? mfma(bv, af, acc[t]) : mfma(af, bv, acc[t]);
+    }
+  };
+  if constexpr (KRES > 0) {
+#pragma unroll
+    for (int s = 0; s < KRES; ++s) step(lds_b128(res + s * (1024 * NW)), s);
+  }
+  // rolled over all ring periods but the tail (one load per k-step: the vmcnt waits of the rolled
   // loop assume a uniform count) ...
 #pragma unroll 1
-  for (int s0 = 0; s0 < KS - (PD + 1); s0 += PD + 1) {
+  for (int s0 = KRES; s0 < KS - TL; s0 += PD + 1) {
 #pragma unroll
     for (int u = 0; u <= PD; ++u) {
       const int s = s0 + u;
       const bf16x8 af = ring[u];
       ring[(u + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(wfrag + static_cast<int64_t>(16 * H) * (s + PD));
-      const char *p = rowp + 16 * ((2 * s + h) ^ swz);
-#pragma unroll
-      for (int t = 0; t < NTILE; ++t) acc[t] = mfma(af, lds_b128(p + t * 32 * (2 * H)), acc[t]);
+      step(af, s);
     }
   }
-  // ... and the last period peeled: only its first k-step still prefetches (step KS-1), so no
+  // ... and the tail peeled: only its first steps still prefetch (up to step KS-1), so no
   // redundant weight loads are in flight when the pass ends (a wait on them, forced by a
   // register reuse after the pass, cost a full L2 round trip per pass)
 #pragma unroll
-  for (int u = 0; u <= PD; ++u) {
-    const int s = KS - (PD + 1) + u;
-    const bf16x8 af = ring[u];
+  for (int u = 0; u < TL; ++u) {
+    const int s = KS - TL + u;
+    const bf16x8 af = ring[u % (PD + 1)];
     if (s + PD < KS)
       ring[(u + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(wfrag + static_cast<int64_t>(16 * H) * (s + PD));
-    const char *p = rowp + 16 * ((2 * s + h) ^ swz);
-#pragma unroll
-    for (int t = 0; t < NTILE; ++t) acc[t] = mfma(af, lds_b128(p + t * 32 * (2 * H)), acc[t]);
+    step(af, s);
   }
   mfma_drain(acc);
 }

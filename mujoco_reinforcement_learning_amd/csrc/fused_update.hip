@@ -73,7 +73,18 @@ struct Lds {
   // one is staged (the two buffers alternate chunk by chunk)
   static constexpr int X2 = WHT + (F32A2 ? 0 : H * 32);
   static constexpr int TOTAL = X2 + (F32A2 ? 0 : R * 64);
-  static_assert(TOTAL <= 163840, "LDS budget");
+  // ReLU, resident schedule (SCHED bit 1): D2 overwrites the wave's own A2 columns and D1 never
+  // goes to LDS, so the D2 region above is free for the whole kernel and holds the wave-private
+  // copies of the first KRES_D k-steps of the W1^T image (fused_common.h mlp_pass KRES: 1 KB per
+  // k-step and wave, the image's own order); the head's z exchange, which borrowed the D2 region,
+  // and KRES_F k-steps of the W1 image sit behind the other regions
+  static constexpr int KRES_D = R * PITCH / (NW * 1024);
+  static constexpr int KRES_F = 1;
+  static constexpr int RES = D2;
+  static constexpr int XCH = TOTAL;                              // f32 [8 waves][64 lanes][2]
+  static constexpr int RESF = XCH + NW * 64 * 8;
+  static constexpr int TOTAL_RES = RESF + KRES_F * NW * 1024;
+  static_assert(TOTAL <= 163840 && (F32A2 || TOTAL_RES <= 163840), "LDS budget");
   static_assert(R * PITCH <= A2BYTES, "D1 image must fit in the a2 region");
 };
 
@@ -643,6 +654,19 @@ __device__ __forceinline__ void mfma16_drain(f32x4 &acc) { asm volatile("s_nop 1
 //          3, and X(c) stays in the second X buffer; phase 7 and the chunk's closing barrier go
 //          away (the last chunk's dW0 runs after the loop).  Same MFMA chain into gw0 in the same
 //          order: bitwise the same gradient.
+//   bit 1  (with bit 0; the default, round 12) the RESIDENT schedule: fewer L2 bytes per streamed
+//          pass.  d2 is stored over the wave's own a2 columns (phase 5 reads them first) and D1
+//          never goes to LDS: phase 6b's product runs transposed (mlp_pass SWAP), so after eight
+//          v_permlane32_swap the accumulators ARE the A operand of dW0 += D1^T X(c), issued right
+//          there against X(c) (no deferral, no after-loop dW0, no prologue zeroing; the two X
+//          buffers stay, a fast wave stages X(c+1) while a slow one reads X(c)); db0 is summed per
+//          feature lane in rs16's association.  The freed D2 region holds the wave-private copy
+//          of the first 4 k-steps of the W1^T image and 8 KB behind the other regions the first
+//          k-step of W1 (mlp_pass KRES), filled once per launch by LDS-DMA and read by all of the
+//          workgroup's chunks.  Barriers: the all-column readers of a2 (head z) finish before
+//          phase 4's barriers, the all-column readers of d2 (dW1, dgrad) before the next chunk's
+//          phase-0 barrier, and phase 3 rewrites the region only after that one.  Same operands,
+//          same MFMA chains, same sums: bitwise the same gradient.
 // Measured and dropped (round 6): the head dW inside phase 6a (a tie); the next
 // chunk's layer 0 hoisted behind the dgrad pass with phases 0 and 1 removed (16 spilled VGPRs,
 // 10-17 % slower); the deferred dW0 issued after the L1 pass (3 % slower) or without the
@@ -652,14 +676,19 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
                                            uint64_t *stamps) {
   static_assert(H == 32 * NW, "wave w owns feature tile w");
   constexpr bool F32A2 = ACT != PPO_ACT_RELU;
-  constexpr bool DEFER_DW0 = (SCHED & 1) && !F32A2;
-  bool have_prev = false;  // DEFER_DW0: a previous chunk's dW0 is pending
+  constexpr bool RESIDENT = (SCHED & 2) && !F32A2;
+  static_assert(!(SCHED & 2) || (SCHED & 1), "the resident schedule keeps the two X buffers");
+  constexpr bool X2BUF = (SCHED & 1) && !F32A2;          // X(c) and X(c +- 1) in alternating buffers
+  constexpr bool DEFER_DW0 = X2BUF && !RESIDENT;         // dW0 of chunk c in chunk c + 1's phase 2
+  [[maybe_unused]] bool have_prev = false;  // DEFER_DW0: a previous chunk's dW0 is pending
   using L = Lds<H, F32A2>;
   constexpr int z = ACTOR ? 0 : 1;
+  constexpr int KRES_D = RESIDENT ? L::KRES_D : 0;  // resident k-steps of the dgrad pass ...
+  constexpr int KRES_F = RESIDENT ? L::KRES_F : 0;  // ... and of the L1 pass
   char *ximg = lds + L::X;        // this chunk's X image
   char *xprev = lds + L::X2;      // DEFER_DW0: the previous chunk's (its dW0 runs in phase 2)
   char *const a1img = lds + L::A1;
-  char *const d2img = lds + L::D2;
+  char *const d2img = lds + (RESIDENT ? L::A2 : L::D2);  // RESIDENT: in place of a2, phase 5
   char *const a2img = lds + L::A2;
   char *const d1img = lds + L::A2;  // after phase 5
   char *const whb = lds + L::WHB;
@@ -673,7 +702,9 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
   int tid = tid0, lane = tid & 63, r = lane & 31, h = lane >> 5;
   // Lane-derived LDS addresses are loop-invariant across chunks; re-deriving them from an
   // opaque copy of the lane ids in every phase keeps the compiler from hoisting (and spilling)
-  // dozens of them out of the chunk loop.
+  // dozens of them out of the chunk loop.  RESIDENT_WAVE (phases 0 and 4 of the resident
+  // schedule): the wave index too, whose hoisted addresses were what spilled there.
+#define RESIDENT_WAVE() (RESIDENT ? tid >> 6 : w)
 #define OPAQUE_LANE()             \
   tid = tid0;                     \
   asm volatile("" : "+v"(tid));   \
@@ -751,6 +782,21 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
                                          (lds_void *)(lds + r.lds + 1024 * cc), 16, 0, 0);
     }
   }
+  if constexpr (RESIDENT) {
+    // the wave's fragments of the first KRES_D k-steps of W1^T (and KRES_F of W1), by the same
+    // LDS-DMA (the weights change with every optimizer step: copied in every launch)
+    typedef __attribute__((address_space(3))) void lds_void;
+    const char *const srct = reinterpret_cast<const char *>(N.w1bt);
+    const char *const srcf = reinterpret_cast<const char *>(N.w1b);
+#pragma unroll
+    for (int s = 0; s < KRES_D; ++s)
+      __builtin_amdgcn_global_load_lds(gptr(srct + (s * NW + w) * 1024 + 16 * lane),
+                                       (lds_void *)(lds + L::RES + (s * NW + w) * 1024), 16, 0, 0);
+#pragma unroll
+    for (int s = 0; s < KRES_F; ++s)
+      __builtin_amdgcn_global_load_lds(gptr(srcf + (s * NW + w) * 1024 + 16 * lane),
+                                       (lds_void *)(lds + L::RESF + (s * NW + w) * 1024), 16, 0, 0);
+  }
   const float *const hbias = reinterpret_cast<const float *>(lds + L::HS);
   uint64_t xpre = load_half(blockIdx.x, i_first, tid0, false);
   bool xok = row_ok(blockIdx.x, i_first, tid0);
@@ -809,7 +855,7 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
     // ---- phase 0: the chunk's rows (loaded during the previous chunk) -> X image and the row
     //      scalars (actions, old log-prob, advantage, value target: 64 x 64 B); W0 fragments;
     //      the next chunk's row indices ----
-    if constexpr (DEFER_DW0) {  // X(c) into the buffer X(c-2) used; X(c-1) stays for its dW0
+    if constexpr (X2BUF) {  // X(c) into the buffer X(c-2) used; X(c-1) stays for its dW0
       char *const t = ximg;
       ximg = xprev;
       xprev = t;
@@ -825,14 +871,14 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
       if constexpr (F32A2)
         w0f[s] = *reinterpret_cast<const bf16x8 *>(N.w0b + (32 * w + r) * kFusedKX + 16 * s + 8 * h);
       else
-        w0f[s] = lds_b128(lds + L::W0 + x_off(32 * w + r, 2 * s + h));
+        w0f[s] = lds_b128(lds + L::W0 + x_off(32 * RESIDENT_WAVE() + r, 2 * s + h));
     }
     lds_sync();
     STAMP_AT(0);
 
     // ---- phase 1: a1 = act(W0 x + b0) -> A1 image ----
     OPAQUE_LANE();
-    wring_prime<H>(w_frag_base<H>(N.w1b, w, lane), ring);  // for phase 2
+    wring_prime<H, KRES_F>(w_frag_base<H>(N.w1b, w, lane), ring);  // for phase 2
     {
       f32x16 acc[2];
 #pragma unroll
@@ -885,7 +931,8 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int e = 0; e < 16; ++e) a2[t][e] = 0.f;
-    mlp_pass<H>(w_frag_base<H>(N.w1b, w, lane), a1img, r, h, ring, a2);
+    mlp_pass<H, 2, KRES_F>(w_frag_base<H>(N.w1b, w, lane), a1img, r, h, ring, a2,
+                           lds + L::RESF + 1024 * w + 16 * lane);
     *reinterpret_cast<uint64_t *>(lds + L::SROW + tid0 * 8) = sok_c ? srow_c : 0;  // landed during phases 1-2
     STAMP_AT(2);
 
@@ -917,7 +964,8 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
     //      16 (w & 3) + 4 (lane >> 4) + 2 (w >> 2) + {0, 1} ----
     OPAQUE_LANE();
     {
-      const int n = lane & 15, qg = lane >> 4, tile = w & 3, half = w >> 2;
+      const int n = lane & 15, qg = lane >> 4;
+      const int tile = RESIDENT_WAVE() & 3, half = RESIDENT_WAVE() >> 2;
       const float *const srl = reinterpret_cast<const float *>(lds + L::SROW);
       const int lr0 = 16 * tile + 4 * qg + 2 * half;  // this lane's two rows: lr0, lr0 + 1
       // Every LDS operand of the loss is read here, unconditionally (in-range addresses; masked
@@ -940,8 +988,8 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
       const float h_lsd = ACTOR ? hbias[32 + n] : 0.f, h_ivar = ACTOR ? hbias[48 + n] : 0.f;
       // K split between the wave pair: wave half 0 sums k-steps 0..H/64-1, half 1 the rest
       // (half the LDS reads and MFMAs per wave); each hands the partner the two rows it keeps
-      // through the (still free) D2 region.  z = P_lo + P_hi on both sides (commutative), the
-      // same order as the rollout's policy kernel.
+      // through the (still free) D2 region (RESIDENT: a region of its own).  z = P_lo + P_hi on
+      // both sides (commutative), the same order as the rollout's policy kernel.
       f32x4 zacc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = half * (H / 64); s < (half + 1) * (H / 64); ++s) {
@@ -955,7 +1003,8 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
         zacc = mfma16(av, lds_b128(whb + n * HeadImg<H>::PITCH + 2 * (32 * s + 8 * qg)), zacc);
       }
       mfma16_drain(zacc);
-      float *const xch = reinterpret_cast<float *>(lds + L::D2);  // [8 waves][64 lanes][2]
+      // [8 waves][64 lanes][2]
+      float *const xch = reinterpret_cast<float *>(lds + (RESIDENT ? L::XCH : L::D2));
       *reinterpret_cast<float2 *>(xch + 2 * (w * 64 + lane)) =
           half ? make_float2(zacc[0], zacc[1]) : make_float2(zacc[2], zacc[3]);
       lds_sync();
@@ -1017,8 +1066,31 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
     lds_sync();
     STAMP_AT(4);
 
+    // head dW += dz^T a2 over the chunk's 64 rows: wave w's two 16-feature tiles
+#define HEAD_DW()                                                                                 \
+  _Pragma("unroll") for (int ks = 0; ks < R / 32; ++ks) {                                         \
+    const bf16x8 af = lds_b128(dztimg + (lane & 15) * kDzTPitch + 2 * (32 * ks + 8 * (lane >> 4))); \
+    _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                               \
+      bf16x8 bv;                                                                                  \
+      if constexpr (F32A2) {                                                                      \
+        float v[8];                                                                               \
+        _Pragma("unroll") for (int j = 0; j < 8; ++j) v[j] =                                      \
+            a2f[(32 * ks + 8 * (lane >> 4) + j) * (L::A2P / 4) + 32 * w + 16 * u + (lane & 15)]; \
+        bv = pack8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]));     \
+      } else {                                                                                    \
+        bv = tr_frag16(a2img, L::PITCH, 32 * ks, 32 * w + 16 * u, lane);                          \
+      }                                                                                           \
+      ghw[u] = mfma16(af, bv, ghw[u]);                                                            \
+    }                                                                                             \
+  }
     // ---- phase 5: d2 = (dz . W_h) * act'(a2) on MFMA -> bias grad, D2 image; head dW ----
+    // RESIDENT: d2 overwrites the a2 the wave read it from -- its own columns, which phase 5 alone
+    // reads (yb and the head-dW fragments, both taken before the d2 stores: the head dW runs
+    // first, its MFMA chain into ghw in the same order).  The all-column readers of a2 (head z)
+    // finished before phase 4's barriers; the all-column readers of d2 (dW1, dgrad) finish before
+    // the next chunk's phase-0 barrier, and phase 3 rewrites the region only after that barrier.
     OPAQUE_LANE();
+    if constexpr (RESIDENT) HEAD_DW()
     {
       // the A operand W_h^T of the wave's features, both row tiles' dz fragments and (ReLU) the
       // bf16 a2 values act' needs, all read up front: one LDS round trip for the phase's inputs
@@ -1070,24 +1142,7 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
       }
       gb1 += rs16(bsum, lane);
     }
-    // head dW += dz^T a2 over the chunk's 64 rows: wave w's two 16-feature tiles
-#define HEAD_DW()                                                                                 \
-  _Pragma("unroll") for (int ks = 0; ks < R / 32; ++ks) {                                         \
-    const bf16x8 af = lds_b128(dztimg + (lane & 15) * kDzTPitch + 2 * (32 * ks + 8 * (lane >> 4))); \
-    _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                               \
-      bf16x8 bv;                                                                                  \
-      if constexpr (F32A2) {                                                                      \
-        float v[8];                                                                               \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) v[j] =                                      \
-            a2f[(32 * ks + 8 * (lane >> 4) + j) * (L::A2P / 4) + 32 * w + 16 * u + (lane & 15)]; \
-        bv = pack8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]));     \
-      } else {                                                                                    \
-        bv = tr_frag16(a2img, L::PITCH, 32 * ks, 32 * w + 16 * u, lane);                          \
-      }                                                                                           \
-      ghw[u] = mfma16(af, bv, ghw[u]);                                                            \
-    }                                                                                             \
-  }
-    HEAD_DW()
+    if constexpr (!RESIDENT) HEAD_DW()
     lds_sync();
     STAMP_AT(5);
 
@@ -1096,7 +1151,7 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
     // reads and spills).  The dgrad weight ring is primed first so its L2 latency hides behind
     // this LDS-only phase.
     OPAQUE_LANE();
-    wring_prime<H>(w_frag_base<H>(N.w1bt, w, lane), ring);
+    wring_prime<H, KRES_D>(w_frag_base<H>(N.w1bt, w, lane), ring);
     // the next chunk's states: in flight until the next phase 0
     xpre = load_half(chunk + G, inext, tid, false);
     xok = row_ok(chunk + G, inext, tid);
@@ -1123,9 +1178,68 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-      mlp_pass<H>(w_frag_base<H>(N.w1bt, w, lane), d2img, r, h, ring, acc);
+      mlp_pass<H, 2, KRES_D, RESIDENT>(w_frag_base<H>(N.w1bt, w, lane), d2img, r, h, ring, acc,
+                                       lds + L::RES + 1024 * w + 16 * lane);
       STAMP_AT(7);
       OPAQUE_LANE();
+      if constexpr (RESIDENT) {
+        // The product came out transposed (mlp_pass SWAP): acc[t][e] = d1 pre-activation of
+        // feature 32w + r, row 32t + reg_feature(e, h).  v_permlane32_swap of registers (8u + e,
+        // 8u + 4 + e) hands each half the other's four rows, leaving rows 16 (2t + u) + 8h + 0..7
+        // in registers 8u + 0..7 -- the A-operand order tr_frag(d1img, 16 ks, 32w) returned, so
+        // D1 goes from the accumulators straight into dW0 += D1^T X(c): the same bf16 operands in
+        // the same chain order as the deferred form, never through LDS.  The a1 signs come in
+        // the same order from a transposed read of the wave's own a1 columns.
+        // One row tile at a time, as phase 5: its two X fragments and a1 signs live with one
+        // accumulator tile.
+        // x[8u + j]: the bias-gradient term of row 16u + 8h + j of a tile, tile 0 then tile 1
+        float x[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) x[e] = 0.f;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          bf16x8 fx[2];
+          uint4 ys[2];
+#pragma unroll
+          for (int u = 0; u < 2; ++u) {
+            fx[u] = tr_frag_x(ximg, 16 * (2 * t + u), lane);
+            ys[u] = __builtin_bit_cast(uint4, tr_frag(a1img, L::PITCH, 16 * (2 * t + u), 32 * w, lane));
+          }
+#pragma unroll
+          for (int u = 0; u < 2; ++u) {
+            float d[8];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[t][8 * u + e]),
+                                                              __float_as_uint(acc[t][8 * u + 4 + e]), false, false);
+              d[e] = __uint_as_float(p[0]);
+              d[4 + e] = __uint_as_float(p[1]);
+            }
+            const uint4 yv = ys[u];
+            const uint32_t yw[4] = {yv.x, yv.y, yv.z, yv.w};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              d[j] = act_backward(d[j], (j & 1) ? bf_hi(yw[j >> 1]) : bf_lo(yw[j >> 1]), ACT);
+              x[8 * u + j] += d[j];
+            }
+            const uint4 fdw = make_uint4(pack2(d[0], d[1]), pack2(d[2], d[3]), pack2(d[4], d[5]), pack2(d[6], d[7]));
+            gw0 = mfma(__builtin_bit_cast(bf16x8, fdw), fx[u], gw0);
+          }
+        }
+        // db0 of feature 32w + r over the tile rows in rs16's association: rows m, m ^ 16 (in
+        // lane), then m ^ 8 (the other half: one exchange, each half taking four of the eight
+        // sums), then classes i, 7 - i, then (c0 + c2) + (c1 + c3), the halves' sums meeting last
+        float a[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a[j] = x[j] + x[8 + j];
+        const auto pair_sum = [&](float lo_keep, float hi_keep) {
+          const auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(lo_keep), __float_as_uint(hi_keep), false, false);
+          return __uint_as_float(p[0]) + __uint_as_float(p[1]);
+        };
+        const float ca = pair_sum(a[0], a[1]) + pair_sum(a[7], a[6]);  // h = 0: c0, h = 1: c1
+        const float cb = pair_sum(a[2], a[3]) + pair_sum(a[5], a[4]);  // h = 0: c2, h = 1: c3
+        gb0 += pair_sum(ca + cb, ca + cb);
+      } else {
       // act'(a1): ReLU needs only the sign, which the bf16 image keeps exactly; tanh / ELU
       // recompute this wave's f32 a1 tile (the phase-1 product; X is still resident), one row
       // tile at a time
@@ -1170,6 +1284,7 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
         }
       }
       gb0 += rs16(bsum, lane);
+      }
     }
     STAMP_AT(8);
 
@@ -1178,7 +1293,7 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
     //      chunk's phase 2 (or after the loop), and no closing barrier: the next chunk's X goes to
     //      the other buffer, and every other region it writes before its phase-0 barrier is
     //      read by no wave after this chunk's phase-5 barrier ----
-    if constexpr (!DEFER_DW0) {
+    if constexpr (!X2BUF) {
       OPAQUE_LANE();
       {
         // every transposed fragment read issued first (16 ds_read_b64_tr_b16, 32 registers: the
@@ -1213,6 +1328,7 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
   }
 #undef STAMP_AT
 #undef OPAQUE_LANE
+#undef RESIDENT_WAVE
 #undef HEAD_DW
 #undef DEFERRED_DW0
 
@@ -1242,8 +1358,9 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
   if ((lane & 1) == 0) {
     const int f = 32 * w + rs16_feature(lane);
     if (N.b1) slab[N.off_b1 + f] = gb1;
-    if (N.b0) slab[N.off_b0 + f] = gb0;
+    if (!RESIDENT && N.b0) slab[N.off_b0 + f] = gb0;
   }
+  if (RESIDENT && h == 0 && N.b0) slab[N.off_b0 + 32 * w + r] = gb0;  // summed per feature lane
   // head dW (a, f) row-major [A_net][H]
   const int na = ACTOR ? A : 1;
 #pragma unroll
@@ -1305,7 +1422,8 @@ __device__ __forceinline__ void fused_body(const FusedArgs &q, const FusedNet &N
 
 template <int H, int ACT, int NA, bool STAMP, int SCHED = 0>
 __global__ __launch_bounds__(NT, 1) void fused_update_kernel(FusedArgs q, uint64_t *stamps) {
-  __shared__ __attribute__((aligned(16))) char lds[Lds<H, ACT != PPO_ACT_RELU>::TOTAL];
+  using L = Lds<H, ACT != PPO_ACT_RELU>;
+  __shared__ __attribute__((aligned(16))) char lds[(SCHED & 2) && ACT == PPO_ACT_RELU ? L::TOTAL_RES : L::TOTAL];
   if (blockIdx.y == 0) fused_body<H, ACT, NA, true, STAMP, SCHED>(q, q.net[0], lds, stamps);
   else fused_body<H, ACT, 1, false, STAMP, SCHED>(q, q.net[1], lds, stamps);
 }
@@ -1426,16 +1544,16 @@ int step_tail_launch(const ReduceArgs &r, const TailArgs &t_in, const TimRec &re
   return 0;
 }
 
-// PPO_FUSED_SCHED=0|1: the ReLU kernel's phase schedule (fused_body SCHED; A/B knob, bitwise the
+// PPO_FUSED_SCHED=0|1|3: the ReLU kernel's phase schedule (fused_body SCHED; A/B knob, bitwise the
 // same gradient for every value), read at every launch so one process can compare them
 static int env_fused_sched() {
   const char *v = getenv("PPO_FUSED_SCHED");
-  return v ? atoi(v) : 1;  // default: dW0 deferred (round 6: 1-4 % faster per launch, bitwise equal)
+  return v ? atoi(v) : 3;  // default: the resident schedule (round 12; bitwise equal)
 }
 
 int fused_sched(int act) {
   const int s = env_fused_sched();
-  return act == PPO_ACT_RELU && s == 1 ? 1 : 0;
+  return act == PPO_ACT_RELU && (s == 1 || s == 3) ? s : 0;
 }
 
 template <int ACT, int NA, int SCHED>
@@ -1452,6 +1570,7 @@ static void launch_na(const FusedArgs &q, const TimRec &rec, hipStream_t st) {
   if constexpr (ACT == PPO_ACT_RELU) {
     const int sched = fused_sched(ACT);
     if (sched == 1) return launch_sched<ACT, NA, 1>(q, rec, st);
+    if (sched == 3) return launch_sched<ACT, NA, 3>(q, rec, st);
   }
   launch_sched<ACT, NA, 0>(q, rec, st);
 }
